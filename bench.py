@@ -16,7 +16,13 @@ full Gauss-Newton iterations per trajectory (tol = 0): residual + Jacobian,
 J^T W J / J^T W r assembly, register-tiled Cholesky, two triangular solves,
 update.  value = (all ranks) sum of B_r * P * GN_ITERS * K / max-rank wall.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--global-batch G] [--weak [--batch B]]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                       [--global-batch G] [--weak [--batch B]]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full``
+adds the legs that take runs of their own (the CPU port baseline of the same iteration).
+``--dump-outputs DIR`` writes what the last timed step returned (X, cost, iters, status of
+this rank's trajectories) as DIR/<name>.npy, float64; the inputs are seeded, so two builds
+run with the same arguments compare output for output.
 N > 1: under torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE set) each process is one
 rank; run plainly, bench.py starts the N ranks itself (mhe.launch, before any GPU call)
 and exits with their code.
@@ -144,6 +150,17 @@ def rank_workload(world, rank, global_batch=1024, weak=False, batch=1024, N=100)
     return configs.make_c2(B=global_batch, seed=1, N=N, shard=dist.shard_range(global_batch, world, rank))
 
 
+def dump_outputs(path, outs, rank, world):
+    """What a caller of the timed path receives from its last step, as float64 .npy files:
+    X (B, P, n), cost (B,), iters (B,), status (B,) of this rank's trajectories (1024 C2
+    trajectories are 1.7 MB).  One rank writes <name>.npy; rank r of several writes
+    <name>.rank<r>.npy, its shard of the batch."""
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, t in zip(("X", "cost", "iters", "status"), outs):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,7 +173,13 @@ def main():
                     help="weak scaling instead: --batch trajectories per GPU, a seeded batch per rank")
     ap.add_argument("--batch", type=int, default=1024, help="trajectories per GPU with --weak")
     ap.add_argument("--iters", type=int, default=GN_ITERS)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU port baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (X, cost, iters, status) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="kept for callers from before --full: no effect on a plain run; with --full, "
+                         "leaves the CPU baseline out")
     ap.add_argument("--cpu-sample", type=int, default=1024)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     args = ap.parse_args()
@@ -215,6 +238,9 @@ def main():
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps  # launches are back to back on `stream`
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, rank, world)
 
     wall = dist.max_over_ranks(wall, dev)
     iters_done = dist.sum_over_ranks(outs[2].sum().item(), dev)
@@ -282,7 +308,7 @@ def main():
             elif same:
                 rec["roofline"]["traffic_note"] = (f"profiles/pmc_summary.json measured build {ps.get('lib_sha')}, "
                                                    f"not this libmhe.so ({lib_digest()}): traffic omitted")
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             rec["cpu_baseline"] = cpu_baseline(w, args.iters, args.cpu_sample, args.cpu_seconds)
         print(json.dumps(rec))
     if world > 1:

@@ -5,8 +5,8 @@ pinned to
   * tests/golden/least_squares.npz -- the reference's own runLeastSquares run on
     two seeded synthetic receivers back to back (gen_golden.py: gen_least_squares);
   * the reference's stored results for the real gnss-multi-receiver logs
-    (data/gnss-multi-receiver/LS_{A,B}.csv), read in place when /root/reference
-    is present (build container only; skipped elsewhere -- nothing is copied).
+    (data/gnss-multi-receiver/LS_{A,B}.csv and the two 50y_moving logs' .mat files,
+    stored under tests/golden/gnss-multi-receiver/).
 GPU tolerance: the kernel solves the normal equations where the reference uses
 pinv(G), and stops on the same ||dx|| < 1e-7 rule, so fixes agree to
 |dx| <= 1e-6 m, lat/lon to 1e-10 deg and velocities to 1e-6 m/s.
@@ -20,7 +20,7 @@ import pytest
 from mhe import _lib
 from oracle import leastsquares as ols
 
-REF_DATA = "/root/reference/data/gnss-multi-receiver"
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gnss-multi-receiver")
 X_TOL, LL_TOL, V_TOL = 1e-6, 1e-10, 1e-6
 
 
@@ -53,7 +53,6 @@ def test_oracle_reproduces_reference_runs(lsfx):
         np.testing.assert_allclose(out["bd"], lsfx[f"{tag}_ls_bias_rate"], rtol=0, atol=1e-9)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data not present (GPU box)")
 def test_oracle_reproduces_reference_stored_fixes():
     """Oracle + this package's loader/geodesy against LS_{A,B}.csv of the reference."""
     from utils import data as gd, utils as gu

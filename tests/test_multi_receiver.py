@@ -10,8 +10,8 @@ and B with per-window parameters and R = 0 slots), zA = zB at every node
   velocities from the reference's runLeastSquares).  Tolerance: states at t = T
   and t = DT within 1e-6 * (1 + max|x|) (x holds clock biases ~3e4 m; the
   pseudorange rows lose log10(|y| / |y - h|) ~ 5 digits to cancellation).
-* Against the reference's stored results, read in place when /root/reference is
-  present (build container):
+* Against the reference's stored results and logs (data/gnss-multi-receiver, the files
+  the script reads, stored under tests/golden/gnss-multi-receiver/):
   - the least-squares fixes the script feeds the NLP (controls, first prior) match
     the stored LS_{A,B}.csv to 1e-7 m -- the data pipeline is the reference's;
   - the stored IPOPT fixes NLP_{A,B}.csv are not the optimum of the objective the
@@ -39,7 +39,7 @@ import pytest
 
 from general_problems import TWO_RX, two_rx_mhe_facade, two_rx_mhe_oracle
 
-REF_DATA = "/root/reference/data/gnss-multi-receiver"
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gnss-multi-receiver")
 
 
 def _synthetic(golden):
@@ -88,7 +88,6 @@ def _ref_inputs():
     return dA, dB, p_ref, outs
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data not present (GPU box)")
 def test_least_squares_inputs_match_stored_ls_csv():
     from utils import utils as gu
     _, _, _, outs = _ref_inputs()
@@ -100,7 +99,6 @@ def test_least_squares_inputs_match_stored_ls_csv():
         assert lla.shape == ref.shape and err_m < 1e-7
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data not present (GPU box)")
 def test_stored_ipopt_fixes_are_not_stationary_for_the_script_objective():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))

@@ -41,7 +41,7 @@ def test_c4_workload_uses_the_logs():
     assert np.array_equal(w.U[0], U)      # setControl's interpolation of the logged controls
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present (GPU box)")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="regenerates the fixture with the reference project's own code and logs, which are not in this repository")
 def test_fixture_regenerates_from_the_reference_logs(tmp_path):
     import sys
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -1,10 +1,10 @@
 #!/bin/bash
-# Copy one tools/reproduce.sh run's outputs (gpurun_out/, tag $1) into profiles/ under the
+# Copy one tools/reproduce.sh run's outputs ($MHE_OUT, default results/; tag $1) into profiles/ under the
 # round name $2 (e.g. r06): the files DESIGN.md cites.
 set -e
 T=${1:?usage: tools/collect_records.sh <run tag> <round>}; R=${2:?round}
 cd "$(dirname "$0")/.."
-G=gpurun_out; P=profiles
+G=${MHE_OUT:-results}; P=profiles
 cp $G/pmc_summary_$T.json $P/pmc_summary.json
 cp $G/${T}_kernel_stats.csv $P/${R}_kernel_stats.csv
 cp $G/${T}_bench.log $P/${R}_bench.log

@@ -1,6 +1,6 @@
 """Why the oracle replica of gnss-multi-receiver.py disagrees with the stored IPOPT
-fixes (data/gnss-multi-receiver/NLP_{A,B}.csv) -- build-container diagnostic (reads
-/root/reference data files as text / .mat / .csv only; never on the GPU box).
+fixes (data/gnss-multi-receiver/NLP_{A,B}.csv) -- a CPU diagnostic on the reference's
+logs and stored results, read from tests/golden/gnss-multi-receiver/ (.mat / .csv).
 
 For each window the replica (tests/general_problems.two_rx_mhe_oracle, Gauss-Newton on
 the reference objective, W eliminated) reaches J*.  Fixing the horizontal positions of
@@ -26,7 +26,7 @@ from oracle import gn_general as gg  # noqa: E402
 from oracle import leastsquares as ols  # noqa: E402
 from utils import data as gd, utils as gu  # noqa: E402
 
-REF = "/root/reference/data/gnss-multi-receiver"
+REF = os.path.join(ROOT, "tests", "golden", "gnss-multi-receiver")
 
 
 def main(n_windows=6, penalty=1e8):

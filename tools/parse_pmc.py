@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "nlp-filter_amd"))
 from mhe._lib import lib_digest  # noqa: E402
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-out = os.path.join(ROOT, "gpurun_out")
+out = os.path.join(ROOT, os.environ.get("MHE_OUT", "results"))  # the folder tools/profile_round.sh wrote
 
 
 def rows(pass_name):

@@ -1,23 +1,24 @@
 #!/bin/bash
 # Instruction mix and MFMA busy of the large-system kernels (run on the GPU box):
-#   tools/sq_big.sh <C3|C4> <B> <tag>   -> gpurun_out/sqbig_<tag>_{1,2}/, summary on stdout
+#   tools/sq_big.sh <C3|C4> <B> <tag>   -> $MHE_OUT/ (default results/): sqbig_<tag>_{1,2}/, summary on stdout
 # Separate --pmc passes (each within the per-block counter limits), --kernel-trace none.
 set -e
 CFG=$1; B=$2; TAG=$3
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export MHE_OUT=${MHE_OUT:-results}; O=$MHE_OUT; mkdir -p "$O"
 R="python tools/bench_big.py $CFG $B 1"
 i=0
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM" \
            "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY"; do
   i=$((i+1))
-  timeout -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d gpurun_out/sqbig_${TAG}_$i -o run -- $R > gpurun_out/sqbig_${TAG}_$i.log 2>&1
+  timeout -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d $O/sqbig_${TAG}_$i -o run -- $R > $O/sqbig_${TAG}_$i.log 2>&1
 done
 python - "$TAG" <<'PY'
-import csv, glob, sys, collections
+import csv, glob, os, sys, collections
 tag = sys.argv[1]
 # per kernel: per dispatch sums (GRBM_GUI_ACTIVE: max over instances = one XCD's active cycles x 8 reported)
 acc = collections.defaultdict(lambda: collections.defaultdict(lambda: collections.defaultdict(float)))
-for f in glob.glob(f"gpurun_out/sqbig_{tag}_*/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(f"{os.environ['MHE_OUT']}/sqbig_{tag}_*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"].split("<")[0].replace("void mhe::", "").strip()
         if not k.startswith("k_big"):

@@ -111,7 +111,7 @@ extern "C" {
  * the size queries) unless it equals this build's sizeof -- a binding that
  * declares an older or truncated struct is refused before any later field is
  * read.  (mhe/_lib.py sets it in the ctypes constructors.) */
-#define MHE_ABI_VERSION 7
+#define MHE_ABI_VERSION 8
 
 typedef struct mhe_dims {
   int32_t struct_size;  /* = sizeof(mhe_dims)                                */
@@ -429,6 +429,39 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
                         const double* Y, const double* PAR, int64_t par_bstride,
                         const double* x0, double* H, double* g, double* cost, int32_t* status,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Posterior covariance of the state estimate at query times (ABI v8).
+ *
+ * The objective is r^T W r, so H = J^T W J at the point X is the information matrix of
+ * the whole trajectory, and with S_t = phi(t)^T (x) I_n (the Lagrange row extractSolution
+ * uses)  Cov[x(t)] = S_t H^-1 S_t^T.  The call assembles H at X exactly as a solve does
+ * (Huber IRLS weights, the per-solve Rw), runs the solve's own Cholesky factorization
+ * H = U^T U (on the large-system path with the pivots refined once more) and sweeps the query columns through the factor: Z = U^-T S_t^T, Cov = Z^T Z
+ * (a multi-column forward substitution; no back substitution, no inverse).
+ *
+ * The result is the inverse of the HALF-Hessian J^T W J of the cost: the covariance when
+ * the weights (Qw, Rw, Pw) are inverse covariances, as in every reference script.
+ * Variable bounds are NOT reflected: the result is the information of the unconstrained
+ * GN model at X, whatever n_bounds is.  Bordered problems (n_extra > 0, n_eq > 0) and
+ * MHE_MEAS_MIXED return MHE_ERR_UNSUPPORTED (a covariance under constraints is a
+ * projected quantity), as does n > 16 on the register-resident path, and a problem
+ * whose query panel (dp x 16 doubles of LDS on top of the solve's) does not fit.
+ *
+ *   at          batch; X0 = the point (B, P, n); U, Y, PAR, x0, Rw and their strides, and
+ *               on the large-system path workspace / workspace_bytes, as for mhe_solve.
+ *               The outputs and max_iter / tol of the struct are not read.
+ *   PhiQ        (n_query, P) DEVICE: Lagrange basis rows at the query times
+ *   cov_out     (B, n_query, n, n), each block symmetric; NaN where status != 0
+ *   status_out  (B) 0, MHE_STATUS_NOT_SPD (bad pivot) or MHE_STATUS_BAD_CONSTANTS
+ *   scratch     large-system path: mhe_cov_scratch_bytes(dims, batch, n_query) bytes of
+ *               device memory, the query columns' storage (the register path keeps them
+ *               in LDS: the query returns 0 and scratch may be NULL).  Host-only query.
+ * Only enqueues work on `stream`; allocates nothing.  A query's block does not depend
+ * on the batch size or on the other query times of the call. */
+size_t mhe_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_query);
+int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at,
+                  const double* PhiQ, int32_t n_query, double* cov_out, int32_t* status_out,
+                  void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Batched extended Kalman filter.

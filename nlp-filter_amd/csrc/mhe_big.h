@@ -179,6 +179,12 @@ struct BigArgs {
                       // (mhe_chol_solve_ws on a KKT system) instead of formed at X
   int asm_zskip;      // k_big_assemble: tiles left of the envelope the previous iteration's
                       // factorization used hold zeros (iterations >= 1 of one launch_big)
+  // k_big_cov (BIG_STAGE_COV): Lagrange rows (nq, P) at the query times, the result
+  // (B, nq, n, n) and the caller's panel storage (mhe_cov_scratch_bytes)
+  const double* PhiQ;
+  int nq;
+  double* cov;
+  double* cov_scratch;
 };
 
 // measurement weights of trajectory b: the per-solve array when given, else the constants'
@@ -1096,7 +1102,7 @@ __device__ __forceinline__ void stage_slab_lds(double* LJ, const double* H, int 
 // form, the block's own rows in the split one), then the diagonal block (panels on wave 0,
 // in-block updates and TRSM on the others; L_Ik to H and LB, L_kk^-T to LT and LTs, y_k to
 // YV, b_I updated).  LDS as k_big_chol's (DT, flag, UN, LJ); a non-SPD pivot sets *flag.
-template <int BIG_JB, bool LL, bool SPLITROWS>
+template <int BIG_JB, bool LL, bool SPLITROWS, bool PREC = false>
 __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int kend, double* H, double* LTg, double* BV,
                                                double* YV, double* sm, int lane, int wave, const int* FI = nullptr) {
   double* DT = sm;
@@ -1336,7 +1342,7 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
 #pragma unroll
       for (int r = 0; r < 4; ++r) DT[64 * r + lane] = c[r];
       wave_lds_sync();
-      const bool bad = panel(DT, UN, lane);
+      const bool bad = panel<PREC>(DT, UN, lane);
       if (bad && lane == 0 && !MHE_BIG_KO) *flag = 1;  // probes keep every trajectory running
       wave_lds_sync();
       block_fwd(DT, BV + 16 * k, YV + 16 * k, lane);  // y_k = L_kk^-1 b_k
@@ -1406,7 +1412,7 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
 // of the block's own rows, then the diagonal block), k_big_rows the rows below it (a launch
 // of its own, one workgroup per 8 rows), SPLIT = 2 the backward solve.  SPLIT = 0: the whole
 // factorization and solve in one launch (the right-looking form, and the A/B baseline).
-template <int BIG_JB, bool LL = false, int SPLIT = 0>
+template <int BIG_JB, bool LL = false, int SPLIT = 0, bool PREC = false>
 __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(BigArgs a, int kfirst) {
   static_assert(SPLIT == 0 || LL, "the split stages are the left-looking factorization's");
   const int b = blockIdx.x;
@@ -1451,7 +1457,7 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
   const int kbeg = SPLIT == 1 ? kfirst : 0, kstop = SPLIT == 1 ? big_split_kend(kfirst, NT) : (SPLIT == 2 ? 0 : NT);
   for (int k0 = kbeg; k0 < kstop; k0 += BIG_KB) {
     const int kend = SPLIT == 1 ? kstop : min(k0 + BIG_KB, NT);
-    big_diag_block<BIG_JB, LL, SPLIT != 0>(a, k0, kend, H, LTg, BV, YV, sm, lane, wave, FI);
+    big_diag_block<BIG_JB, LL, SPLIT != 0, PREC>(a, k0, kend, H, LTg, BV, YV, sm, lane, wave, FI);
     double* LB = LJ;  // the diagonal block's L_Ik' and L_kk^-T (big_diag_block)
     double* LTs = LJ + BIG_LB_TILES * 256;
     if (*flag) break;
@@ -2225,6 +2231,97 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_border(BigArgs a) {
   for (int i = threadIdx.x; i < K; i += BIG_NTHREADS) ws[WL.KS + K * K + K + i] = rw[i];  // w = [dz; lambda]
   if (a.lam)
     for (int i = threadIdx.x; i < nc; i += BIG_NTHREADS) a.lam[(size_t)b * nc + i] = rw[nz + i];
+}
+
+// ------------------------------------------------------------ covariance at query times
+// Cov[x(t_q)] = S_q H^-1 S_q^T, S_q = phi(t_q)^T (x) I_n, after k_big_chol left the factor
+// H = L L^T (L_Ik tiles in place, L_kk^-T in LT):  Z = L^-1 S^T by the forward half of
+// k_big_border's panel sweep applied to the nq n query columns (column q n + c: phi_j(t_q)
+// at the component-major row c Pp + j), then Cov_q = Z_q^T Z_q.  The columns live in the
+// caller's scratch (cov_scratch: KP dp doubles per trajectory, column-major, KP = nq n
+// rounded up to 16) -- BM / ZM are sized by the border and empty here.  use_env: the
+// split factorization's envelope is valid (big_env_first); tiles left of a row's first
+// column are exact zeros and are skipped, as the factorization skipped them.
+template <int n>
+__global__ __launch_bounds__(BIG_NTHREADS) void k_big_cov(BigArgs a, int use_env) {
+  const int b = blockIdx.x;
+  const int nq = a.nq, KQ = nq * n, KP = (KQ + 15) / 16 * 16;
+  double* cov = a.cov + (size_t)b * nq * n * n;
+  if (a.state[b] != BIG_RUNNING) {  // bad constants / bad pivot: no result
+    for (int t = threadIdx.x; t < nq * n * n; t += BIG_NTHREADS) cov[t] = NAN;
+    return;
+  }
+  const BigWs WL = big_ws_layout(a.P, a.M, n, a.NT, a.nz, a.nc);
+  const double* ws = a.ws + (size_t)b * a.ws_stride;
+  const double* H = ws + WL.H;
+  const double* LT = ws + WL.LT;
+  const int NT = a.NT, Pp = a.Pp, dp = 16 * NT;
+  double* ZQ = a.cov_scratch + (size_t)b * KP * dp;
+  const int* FI = MHE_BIG_ENV && use_env ? big_env_first(ws, WL, n) : nullptr;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+  for (int t = threadIdx.x; t < KP * dp; t += BIG_NTHREADS) {
+    const int col = t / dp, r = t - col * dp, ca = r / Pp, j = r - ca * Pp;
+    const int q = col / n, c = col - q * n;
+    ZQ[t] = (col < KQ && c == ca && j < a.P) ? a.PhiQ[(size_t)q * a.P + j] : 0.0;
+  }
+  __syncthreads();
+
+  // MFMA operand layout as in k_big_border: A[i = l&15][m = 4r + (l>>4)], B[m][j = l&15],
+  // C[(l>>4) + 4r][l&15]
+  const int ii = lane & 15, mg = lane >> 4;
+  for (int p0 = 0; p0 < KQ; p0 += 16) {
+    double* Zp = ZQ + (size_t)p0 * dp;
+    auto zload = [&](int blk, int r) { return Zp[(size_t)ii * dp + 16 * blk + 4 * r + mg]; };  // B[m][j]
+    for (int k = 0; k < NT; ++k) {  // Y_k = L_kk^-1 Z_k;  Z_I -= L_Ik Y_k
+      if (wave == 0) {
+        d4 c = {0.0, 0.0, 0.0, 0.0};
+        double av[4], bv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          av[r] = LT[(size_t)k * DTS + (4 * r + mg) * LIS + ii];  // (L^-1)[i][m] = (L^-T)[m][i]
+          bv[r] = zload(k, r);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * k + mg + 4 * r] = c[r];
+      }
+      __syncthreads();
+      for (int I = k + 1 + wave; I < NT; I += BIG_NW) {
+        if (FI && k < FI[I]) continue;  // outside the envelope: L_Ik = 0
+        const double* L = H + (size_t)big_tile_index(I, k, NT) * 256;
+        d4 c;
+        double av[4], bv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          c[r] = Zp[(size_t)ii * dp + 16 * I + mg + 4 * r];
+          av[r] = L[(4 * r + mg) * 16 + ii];  // L_Ik[i][m], k-major tile (negated by the MFMA)
+          bv[r] = zload(k, r);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, MFMA_NEG_A);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * I + mg + 4 * r] = c[r];
+      }
+      __syncthreads();
+    }
+  }
+
+  // Cov_q[ra][cb] = Z_(q,ra) . Z_(q,cb): one wave per upper-triangle entry, mirrored
+  for (int t = wave; t < nq * n * n; t += BIG_NW) {
+    const int q = t / (n * n), e = t - q * n * n, ra = e / n, cb = e - ra * n;
+    if (ra > cb) continue;
+    const double* x = ZQ + (size_t)(q * n + ra) * dp;
+    const double* y = ZQ + (size_t)(q * n + cb) * dp;
+    double s = 0.0;
+    for (int i = lane; i < dp; i += 64) s += x[i] * y[i];
+    s = wave_sum(s);
+    if (lane == 0) {
+      cov[(size_t)q * n * n + ra * n + cb] = s;
+      cov[(size_t)q * n * n + cb * n + ra] = s;
+    }
+  }
 }
 
 // ------------------------------------------------------------ update

@@ -58,7 +58,7 @@ constexpr int MAX_NT = 13;         // padded system <= 208 (register-resident pa
 // rest of the kernel and the allocator spilled tiles to scratch.
 constexpr int MAX_SLOTS = (MAX_NT * (MAX_NT - 1) / 2 + NW - 1) / NW;  // 10 at 8 waves
 
-enum Mode { MODE_SOLVE = 0, MODE_ASSEMBLE = 1, MODE_LINSOLVE = 2 };
+enum Mode { MODE_SOLVE = 0, MODE_ASSEMBLE = 1, MODE_LINSOLVE = 2, MODE_COV = 3 };
 
 // Process-wide A/B options (defined in mhe_gn.hip, set only through the explicit
 // mhe_set_option call of include/mhe.h -- never from the environment): the
@@ -101,7 +101,7 @@ __host__ __device__ inline ConstLayout const_layout(int P, int M, int n, int p, 
 }
 
 struct SmemLayout {  // offsets in doubles
-  int Xs, Vs, FtV, Es, FtE, GE, G, LAM, BV, YV, PB, HB, BAND, ZT, DT, RED, ROWM, UN, XO, ACT, GV, total;
+  int Xs, Vs, FtV, Es, FtE, GE, G, LAM, BV, YV, PB, HB, BAND, ZT, DT, RED, ROWM, UN, XO, ACT, GV, ZP, total;
 };
 
 __host__ __device__ inline int rnd2(int x) { return (x + 1) & ~1; }  // keep 16-B alignment
@@ -117,8 +117,10 @@ __host__ __device__ constexpr int unit_row(int i) { return (i & 1) ? 51 - i : 16
 
 // sb: the small-batch factorization (factor_forward_sb): U block rows double-buffered
 // (PB) and the hand-off tile of the critical-path wave (HB, double-buffered)
+// cov: the 16-column query panel of the covariance sweep (cov_sweep, MODE_COV), last, so
+// that no other offset depends on it
 __host__ __device__ inline SmemLayout smem_layout(int P, int M, int n, int NT, bool nonlinear, bool bounded = false,
-                                                  bool sb = false) {
+                                                  bool sb = false, bool cov = false) {
   SmemLayout S;
   int o = 0;
   const int dp = 16 * NT;
@@ -147,6 +149,7 @@ __host__ __device__ inline SmemLayout smem_layout(int P, int M, int n, int NT, b
   // -g at the iterate, kept for the Armijo test: factor_forward turns BV into the
   // forward-substituted right-hand side in place
   S.GV = o;   o += bounded ? dp : 0;
+  S.ZP = o;   o += cov ? dp * 16 : 0;   // Z (dp x 16), one 16 x 16 block per block row, row-major
   S.total = o;
   return S;
 }
@@ -183,6 +186,9 @@ struct GnArgs {
   double dpar[8];           // mhe_dims.dyn_par (dynamics plug-in params)
   const double* Rw;         // per-solve measurement weights (B|1, M, p, p) or NULL = the constants' Rw
   long long rwstride;       //   (nonlinear measurement models only: a linear h folds Rw into Cc)
+  const double* PhiQ;       // MODE_COV: (nq, P) Lagrange rows at the query times
+  int nq;
+  double* cov;              // MODE_COV: (B, nq, n, n)
 };
 
 #ifdef MHE_DIAG
@@ -1142,15 +1148,22 @@ __device__ __forceinline__ double row0_both(double v) {
   return __longlong_as_double(((long long)h[0] << 32) | (unsigned int)l[0]);
 }
 
-// 1/sqrt(x) for a positive finite pivot: hardware v_rsq_f64 (~1e-9 relative)
-// refined by one Newton step (error squared: ~1 ulp).  Non-positive or
+// 1/sqrt(x) for a positive finite pivot: hardware v_rsq_f64 (5e-8 relative, measured on
+// gfx950) refined by one Newton step (error squared: 4e-15, 18 ulp).  Non-positive or
 // non-finite pivots are flagged by the caller and poison the factor anyway.
 // (Writing the step as four instructions with the halving in the fma's output
 // modifier needs inline asm, and then a wait state of its own after the rsq: no gain.)
+// PREC: a second Newton step.  The pivots' relative error scales the factor's columns, a
+// backward error of twice its size on H; the covariance sweep's factorization of an
+// ill-conditioned H (C3: cond 3.6e8) needs the pivots at the rounding level (mhe_state_cov).
+template <bool PREC = false>
 __device__ __forceinline__ double rsqrt_pivot(double x) {
   const double r = __builtin_amdgcn_rsq(x);
   const double e = fma(-x * r, r, 1.0);  // 1 - x r^2
-  return fma(0.5 * r, e, r);
+  const double r1 = fma(0.5 * r, e, r);
+  if constexpr (!PREC) return r1;
+  const double e1 = fma(-x * r1, r1, 1.0);
+  return fma(0.5 * r1, e1, r1);
 }
 
 // Panel of block k, run by ONE wave (look-ahead: during the previous step's
@@ -1173,6 +1186,7 @@ __device__ __forceinline__ double rsqrt_pivot(double x) {
 // high word in scalar ALU: a pivot passes when its high word is in [1, 0x7FEFFFFF],
 // i.e. positive, finite and >= 2^-1042 -- the larger subnormals pass, zero, the
 // smallest subnormals, negatives, inf and NaN are flagged).
+template <bool PREC = false>
 __device__ __forceinline__ bool panel(double* DTk, const double* UN, int lane) {
   const int i = lane & 15;
   const bool erow = (lane >= 16 && lane < 32);
@@ -1189,7 +1203,7 @@ __device__ __forceinline__ bool panel(double* DTk, const double* UN, int lane) {
   for (int c = 0; c < 16; ++c) {
     const double piv = readlane_d(v[c], c);
     bad |= (unsigned)__double2hiint(piv) - 1u >= 0x7FEFFFFFu;  // high word not in [1, 0x7FEFFFFF]
-    double q = v[c] * rsqrt_pivot(piv);
+    double q = v[c] * rsqrt_pivot<PREC>(piv);
     v[c] = q;
     if (c < 15) {
       // L column c (the row lanes' q) into both 16-lane rows, then for j > c
@@ -1855,6 +1869,13 @@ __device__ inline void bad_constants(const GnArgs& a, int b, int mode) {
   }
 }
 
+// MODE_COV: a trajectory without a result (bad pivot, constants of other dims)
+template <int n>
+__device__ inline void cov_fail(const GnArgs& a, int b, int status) {
+  for (int t = threadIdx.x; t < a.nq * n * n; t += blockDim.x) a.cov[(size_t)b * a.nq * n * n + t] = NAN;
+  if (threadIdx.x == 0) a.status[b] = status;
+}
+
 // projected Newton constants (k_gn_bounded, k_big_linesearch; oracle/gn.py has the same)
 constexpr double EPS_ACT = 1e-6;
 constexpr double ARMIJO_SIGMA = 1e-4;
@@ -1876,6 +1897,96 @@ __device__ __forceinline__ int opaque_s(int x) {
 #define FCL const_layout(opaque_s(a.P), opaque_s(a.M), n, MEAS::p, opaque_s(a.NT))
 #define FSL smem_layout(opaque_s(a.P), opaque_s(a.M), n, opaque_s(a.NT), !MEAS::LINEAR, false, SB)
 
+// ------------------------------------------------------------ covariance sweep (MODE_COV)
+// Cov[x(t)] = S_t H^-1 S_t^T with S_t = phi(t)^T (x) I_n, from the factor H = U^T U that
+// factor_forward left in place (U_kb in the accumulator slots, L_kk^-T in DT):
+// Z = U^-T S_t^T by a multi-column forward substitution, Cov = Z^T Z -- no back
+// substitution, no inverse.  16 / n queries share one 16-column panel (ZP: one row-major
+// 16 x 16 block per block row); column q n + c of the panel is phi_j(t_q) e_c at the
+// node-major row j n + c, padding rows and spare columns 0.  Per block row k:
+//   Y_k = L_kk^-1 Z_k     by every wave that owns a tile (k, b), each for itself (4 MFMAs:
+//                         no barrier between this and the update), and by wave k % NW,
+//                         which adds Y_k^T Y_k to its part of the Gram matrix;
+//   Z_b -= U_kb^T Y_k     by the owner of tile (k, b): the tile's C-layout registers ARE
+//                         the A operand of its transpose (A[i = l&15][m = 4r + (l>>4)] =
+//                         U[4r + (l>>4)][l&15]), Y_k's the B operand -- 4 MFMAs, NEG_A.
+// One workgroup barrier per block row.  A panel column's results depend on that column
+// alone, so a query's block does not depend on which other queries share the call.
+template <int n, int SLOTS>
+__device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL, double* sm, d4 (&acc)[SLOTS],
+                                          int wave, int lane, int stab, int b) {
+  constexpr int QPP = 16 / n;  // queries per panel
+  double* ZP = sm + SL.ZP;
+  const double* DT = sm + SL.DT;
+  const int NT = a.NT, dp = 16 * NT, dn = a.P * n;
+  for (int q0 = 0; q0 < a.nq; q0 += QPP) {
+    const int nql = a.nq - q0 < QPP ? a.nq - q0 : QPP;
+    for (int t = threadIdx.x; t < dp * 16; t += NTHREADS) ZP[t] = 0.0;
+    __syncthreads();
+    for (int t = threadIdx.x; t < nql * dn; t += NTHREADS) {
+      const int ql = t / dn, row = t - ql * dn, j = row / n, c = row - j * n;
+      ZP[row * 16 + ql * n + c] = a.PhiQ[(size_t)(q0 + ql) * a.P + j];
+    }
+    __syncthreads();
+    d4 gram = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int k = 0; k < NT; ++k) {
+      int lane_o = lane, wave_o = wave, stab_o = stab;  // opaque per step, as factor_forward
+      asm volatile("" : "+v"(lane_o));
+      asm volatile("" : "+s"(wave_o));
+      asm volatile("" : "+v"(stab_o));
+      const int sT = slot_start(k, wave_o, NT), sU = slot_start(k + 1, wave_o, NT);
+      const unsigned mT = (1u << sU) - (1u << sT);  // this wave's tiles (k, b), b > k
+      const bool own = wave_o == k % NW;
+      if (mT != 0u || own) {
+        const double* LT = DT + k * DTS;
+        double la[4], zk[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          la[r] = LT[(4 * r + (lane_o >> 4)) * LIS + (lane_o & 15)];  // L^-1[l&15][4r+(l>>4)]
+          zk[r] = ZP[k * 256 + r * 64 + lane_o];
+        }
+        d4 y = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) y = __builtin_amdgcn_mfma_f64_16x16x4f64(la[r], zk[r], y, 0, 0, 0);
+        if (own) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gram = __builtin_amdgcn_mfma_f64_16x16x4f64(y[r], y[r], gram, 0, 0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+          if ((mT >> s) & 1u) {
+            double* zb = ZP + (slot_ij(stab_o, s) & 0xffff) * 256 + lane_o;
+            d4 t;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t[r] = zb[64 * r];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[s][r], y[r], t, 0, 0, MFMA_NEG_A);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) zb[64 * r] = t[r];
+          }
+        }
+      }
+      __syncthreads();  // Z_{k+1} complete; nobody reads Z_k again
+    }
+    // the waves' Gram parts, summed in wave order into block 0 of the (dead) panel
+    for (int w = 0; w < NW; ++w) {
+      if (wave == w) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ZP[r * 64 + lane] = w == 0 ? gram[r] : ZP[r * 64 + lane] + gram[r];
+      }
+      __syncthreads();
+    }
+    // the n x n diagonal block of each query, both triangles from the upper one
+    for (int t = threadIdx.x; t < nql * n * n; t += NTHREADS) {
+      const int ql = t / (n * n), e = t - ql * n * n, ra = e / n, cb = e - ra * n;
+      const int lo = ra < cb ? ra : cb, hi = ra < cb ? cb : ra;
+      a.cov[((size_t)b * a.nq + q0 + ql) * n * n + e] = ZP[(ql * n + lo) * 16 + ql * n + hi];
+    }
+    __syncthreads();
+  }
+}
+
 // MINW (launch bounds' 2nd argument): min waves per SIMD -- 4 = two workgroups (trajectories)
 // per CU, 128 VGPRs; 2 = the small-batch instance (batch <= CUs: one workgroup per CU
 // anyway), which may use 256 VGPRs
@@ -1886,7 +1997,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   static_assert(!SB || (mode == MODE_SOLVE && MINW <= 2 && NW == 8), "small-batch factorization: one workgroup per CU");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const ConstLayout CL = const_layout(a.P, a.M, n, MEAS::p, a.NT);
-  const SmemLayout SL = smem_layout(a.P, a.M, n, a.NT, !MEAS::LINEAR, false, SB);
+  const SmemLayout SL = smem_layout(a.P, a.M, n, a.NT, !MEAS::LINEAR, false, SB, mode == MODE_COV);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x;
@@ -1905,7 +2016,10 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
   if (!tag_ok(a)) {  // constants built for other dims: compute nothing
-    bad_constants(a, b, mode);
+    if constexpr (mode == MODE_COV)
+      cov_fail<n>(a, b, MHE_STATUS_BAD_CONSTANTS);
+    else
+      bad_constants(a, b, mode);
     return;
   }
 
@@ -1970,6 +2084,21 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       }
       for (int t = threadIdx.x; t < dp; t += NTHREADS) a.gout[(size_t)b * dp + t] = -sm[SL.BV + t];
       if (threadIdx.x == 0) a.cost[b] = c1;
+      return;
+    }
+    if constexpr (mode == MODE_COV) {
+      // the system of MODE_ASSEMBLE at X (Huber weights, per-solve Rw), the solve's own
+      // factorization, then the query columns through the factor while it is in registers
+      if constexpr (n <= 16) {
+        build_tiles<DYN, MEAS, SLOTS, HUBER>(FA, FCL, FSL, sm, acc, wave, lane, stab);
+        __syncthreads();
+        if (!factor_forward<SLOTS>(FA, FSL, sm, acc, wave, lane, stab, DIAG_FARGS)) {
+          cov_fail<n>(a, b, MHE_STATUS_NOT_SPD);
+          return;
+        }
+        cov_sweep<n, SLOTS>(a, SL, sm, acc, wave, lane, stab, b);
+        if (threadIdx.x == 0) a.status[b] = MHE_STATUS_CONVERGED;
+      }
       return;
     }
     if (it >= a.max_iter) break;
@@ -2320,11 +2449,11 @@ inline bool meas_info(int id, int n, int& p, int& q, bool& linear) {
 // the large-system path so both paths can be compared on identical inputs.
 // Mixed-row problems, extra variables and equality constraints
 // always take the large-system path (it carries the bordered KKT step).
-inline int smem_bytes(const mhe_dims* dm, int NT, bool bounded = false, bool sb = false) {
+inline int smem_bytes(const mhe_dims* dm, int NT, bool bounded = false, bool sb = false, bool cov = false) {
   int p, q;
   bool lin;
   meas_info(dm->meas_model, dm->n, p, q, lin);
-  return smem_layout(dm->N + 1, dm->M, dm->n, NT, !lin, bounded, sb).total * (int)sizeof(double);
+  return smem_layout(dm->N + 1, dm->M, dm->n, NT, !lin, bounded, sb, cov).total * (int)sizeof(double);
 }
 
 // The register-resident kernel keeps per-row measurement blocks G_i (n x n) in LDS;
@@ -2439,7 +2568,7 @@ struct PairOps {
   // register-resident path: the tile tables of the constants buffer (k_build_cc)
   int (*build_cc)(const mhe_dims* dm, int NT, const double* D, const double* cw, const double* Phi,
                   const double* Qw, const double* Rw, const double* Pw, char* cbuf, hipStream_t st);
-  // register-resident path: one fused launch (MODE_SOLVE / ASSEMBLE / LINSOLVE)
+  // register-resident path: one fused launch (MODE_SOLVE / ASSEMBLE / LINSOLVE / COV)
   int (*gn)(const mhe_dims* dm, GnArgs& a, int batch, int mode, hipStream_t st);
   // large-system path: max_iter iterations of resid -> assemble -> chol (-> border)
   // -> update / line search, then the final residual pass (A.X holds X0 and the
@@ -2483,7 +2612,8 @@ inline GnChoice gn_choice(const mhe_dims* dm, int NT, int batch, int mode, hipSt
   // scaling at 4-8 GPUs: 256 / 128 per GPU)
   c.sb = MHE_GN_SB && mode == MODE_SOLVE && !c.bounded && !c.huber && batch <= device_cus(st) &&
          smem_bytes(dm, NT, false, true) + g_opt_smem_pad <= REG_LDS_LIMIT;
-  c.smem = smem_bytes(dm, NT, c.bounded, c.sb) + g_opt_smem_pad;  // pad: mhe_set_option, occupancy A/B only
+  // pad: mhe_set_option, occupancy A/B only; MODE_COV: the query panel on top (dp x 16)
+  c.smem = smem_bytes(dm, NT, c.bounded, c.sb, mode == MODE_COV) + g_opt_smem_pad;
   return c;
 }
 
@@ -2504,7 +2634,12 @@ int launch_gn(const mhe_dims* dm, GnArgs& a, int batch, int mode, hipStream_t st
                    : k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE>;
     else if (mode == MODE_ASSEMBLE)
       kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE, true> : k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE>;
-    else kern = k_gn<DYN, MEAS, MAX_SLOTS, MODE_LINSOLVE>;
+    else if (mode == MODE_COV) {
+      if constexpr (DYN::n <= 16)
+        kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_COV, true> : k_gn<DYN, MEAS, MAX_SLOTS, MODE_COV>;
+      else
+        return MHE_ERR_UNSUPPORTED;  // a query's n columns must fit one 16-column panel
+    } else kern = k_gn<DYN, MEAS, MAX_SLOTS, MODE_LINSOLVE>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
       return MHE_ERR_HIP;
     hipLaunchKernelGGL(kern, dim3(batch), dim3(NTHREADS), smem, st, a);
@@ -2540,17 +2675,22 @@ struct BigCholPlan {
   int smem, smem_rows, smem_diag;
   bool split;
 };
-inline int big_chol_plan(const BigArgs& A, BigCholPlan& p) {
+// prec: the instances with the pivots' second Newton step (BIG_STAGE_COV)
+inline int big_chol_plan(const BigArgs& A, BigCholPlan& p, bool prec = false) {
   const bool wide = A.NT >= BIG_WIDE_NT;
   p.smem = big_chol_lds(wide ? 8 : 4) * (int)sizeof(double);
   p.smem_rows = big_rows_lds() * (int)sizeof(double);
   const bool ll = g_opt_big_right_looking == 0;
   p.split = ll && (MHE_BIG_SPLIT == 1 || (MHE_BIG_SPLIT == 2 && wide));
   p.mono = wide ? (ll ? k_big_chol<8, true> : k_big_chol<8>) : (ll ? k_big_chol<4, true> : k_big_chol<4>);
+  if (prec)
+    p.mono = wide ? (ll ? k_big_chol<8, true, 0, true> : k_big_chol<8, false, 0, true>)
+                  : (ll ? k_big_chol<4, true, 0, true> : k_big_chol<4, false, 0, true>);
   // the split diagonal stage stages a kb x 4 slab at any width (MHE_BIG_DIAG_REG): the
   // 4-wide instance's LDS, two workgroups per CU
   const bool d4w = MHE_BIG_DIAG_REG != 0;
   p.diag = wide && !d4w ? k_big_chol<8, true, 1> : k_big_chol<4, true, 1>;
+  if (prec) p.diag = wide && !d4w ? k_big_chol<8, true, 1, true> : k_big_chol<4, true, 1, true>;
   p.smem_diag = big_chol_lds(wide && !d4w ? 8 : 4) * (int)sizeof(double);
   p.bwd = wide ? k_big_chol<8, true, 2> : k_big_chol<4, true, 2>;
   for (auto f : {p.mono, p.bwd})
@@ -2668,11 +2808,24 @@ inline int launch_big_resid(const BigArgs& A, int batch, int final_pass, hipStre
 // tiles and BV = -g in the workspace, cost; with z also the per-epoch border sums),
 // BIG_STAGE_FACTOR runs k_big_chol on the workspace's tiles and BV (delta in YV) and,
 // for a bordered system, k_big_border on the border the caller imported (w in KS).
+// BIG_STAGE_COV (mhe_state_cov) runs both at A.X -- the factorization plan a solve would
+// pick -- and then k_big_cov: the query columns A.PhiQ through the factor, A.cov.
 // The state words are set by the caller.
-constexpr int BIG_STAGE_ASSEMBLE = 0, BIG_STAGE_FACTOR = 1;
+constexpr int BIG_STAGE_ASSEMBLE = 0, BIG_STAGE_FACTOR = 1, BIG_STAGE_COV = 2;
 template <class DYN, class MEAS>
 int launch_big_stage(const mhe_dims* dm, BigArgs& A, int batch, int stage, hipStream_t st) {
-  (void)dm;
+  if (stage == BIG_STAGE_COV) {
+    if (A.nz + A.nc > 0) return MHE_ERR_UNSUPPORTED;
+    int rc = launch_big_stage<DYN, MEAS>(dm, A, batch, BIG_STAGE_ASSEMBLE, st);
+    if (rc != MHE_OK) return rc;
+    // the plan a solve would pick, its pivots refined once more (rsqrt_pivot<true>): with the
+    // solve's pivots the C3 covariance sat at 18 times the conditioning floor of the reference
+    BigCholPlan cp;
+    if (big_chol_plan(A, cp, true) < 0) return MHE_ERR_HIP;
+    launch_big_factor(cp, A, batch, st);
+    hipLaunchKernelGGL(k_big_cov<DYN::n>, dim3(batch), dim3(BIG_NTHREADS), 0, st, A, cp.split ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  }
   if (stage == BIG_STAGE_ASSEMBLE) {
     big_pair_plan(A, BigGSupport<MEAS>::get(A.idx, A.n));
     const BigAsmShape sh = big_asm_shape(A);

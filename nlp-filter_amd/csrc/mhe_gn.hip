@@ -618,6 +618,68 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   return ops->gn(dims, a, batch, MODE_SOLVE, st);
 }
 
+// mhe_state_cov's scratch on the large-system path: one cost word per trajectory (the
+// residual pass writes it; 256-B aligned), then the query columns, KP dp doubles per trajectory
+static size_t cov_cost_doubles(int batch) { return ((size_t)batch + 31) & ~size_t(31); }
+
+size_t mhe_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_query) {
+  int NT = 0;
+  if (check_dims(dims, &NT) != MHE_OK || batch < 0 || n_query <= 0) return 0;
+  if (!is_big(dims)) return 0;
+  const size_t KP = ((size_t)n_query * dims->n + 15) / 16 * 16;
+  return sizeof(double) * (cov_cost_doubles(batch) + (size_t)batch * KP * 16 * NT);
+}
+
+int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* PhiQ,
+                  int32_t n_query, double* cov_out, int32_t* status_out, void* scratch, size_t scratch_bytes,
+                  void* stream) {
+  int NT = 0;
+  int rc = check_dims(dims, &NT);
+  if (rc != MHE_OK) return rc;
+  // a covariance under constraints is a projected quantity: not this call's
+  if (dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED) return MHE_ERR_UNSUPPORTED;
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  const int batch = at->batch;
+  if (batch < 0 || n_query <= 0) return MHE_ERR_DIMS;
+  if (!PhiQ || !cov_out || !status_out) return MHE_ERR_NULL;
+  if (batch == 0) return MHE_OK;
+  if (!const_buf || !at->X0 || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) || (dims->q > 0 && !at->PAR) ||
+      (dims->has_prior && !at->x0))
+    return MHE_ERR_NULL;
+  if (at->Rw) {  // as mhe_solve: a linear h folds Rw into the constants
+    int p, q;
+    bool lin;
+    meas_info(dims->meas_model, dims->n, p, q, lin);
+    if (lin) return MHE_ERR_UNSUPPORTED;
+  }
+  const PairOps* ops = find_pair(dims);
+  if (!ops) return MHE_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (is_big(dims)) {
+    if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
+    if (!scratch || scratch_bytes < mhe_cov_scratch_bytes(dims, batch, n_query)) return MHE_ERR_NULL;
+    BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
+    A.n_bounds = 0;  // the unconstrained GN model at X (bounds are not reflected)
+    A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
+    A.Rw = at->Rw; A.rwstride = at->rw_bstride;
+    A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
+    A.cost = (double*)scratch; A.state = status_out;
+    A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
+    const int nb = (batch + 255) / 256;
+    hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
+    rc = ops->big_stage(dims, A, batch, BIG_STAGE_COV, st);
+    if (rc != MHE_OK) return rc;
+    hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status_out);
+    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  }
+  GnArgs a = make_args(dims, const_buf, NT);
+  a.X0 = at->X0; a.U = at->U; a.ustride = at->u_bstride; a.Y = at->Y; a.PAR = at->PAR; a.pstride = at->par_bstride;
+  a.x0 = at->x0; a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.status = status_out;
+  a.PhiQ = PhiQ; a.nq = n_query; a.cov = cov_out;
+  return ops->gn(dims, a, batch, MODE_COV, st);
+}
+
 int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
                int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, double* W, double* F,
                double* E, double* Hm, void* stream) {

@@ -89,6 +89,9 @@ SIGNATURES = {
     "mhe_big_envelope": (c_i32, [_P, c_vp, c_sz, c_i32, c_vp, c_i32, c_vp]),
     "mhe_assemble_kkt_ws": (ctypes.c_int, [_P, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mhe_cov_scratch_bytes": (c_sz, [_P, c_i32, c_i32]),
+    "mhe_state_cov": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp]),
     "mhe_ekf_run": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -443,6 +443,57 @@ class BatchSolver:
             return H, g, cost, status
         return H, g, cost
 
+    def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None):
+        """Posterior covariance of the state at query times (mhe_state_cov): with H = J^T W J
+        at X (the solve's own assembly: Huber weights, per-solve ``Rw``) and S_t = phi(t)^T (x)
+        I_n, cov[b, q] = S_t H^-1 S_t^T, from the solve's Cholesky factor by a forward sweep
+        of the query columns.  Query times ``t`` (Tq,) in [0, T] go through the Lagrange basis
+        extractSolution uses; or pass the basis rows ``Phi`` (Tq, P) directly.  Returns
+        (cov (B, Tq, n, n), status (B,): 0, 2 = not SPD, 4 = bad constants; cov is NaN where
+        status != 0).  The inverse of the half-Hessian: a covariance when the weights are
+        inverse covariances.  Bounds are not reflected; bordered and mixed-row problems are
+        refused (MHE_ERR_UNSUPPORTED)."""
+        self._check_ready()
+        if (t is None) == (Phi is None):
+            raise ValueError("give the query times t or the basis rows Phi (one of them)")
+        if Phi is None:
+            from nlp.collocation import ChebyshevPseudospectralMethod
+            Phi = ChebyshevPseudospectralMethod(self.N, 0, self.T).lagrange_matrix(
+                np.asarray(t, dtype=np.float64).reshape(-1))
+        Phi = np.asarray(Phi.cpu() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64).reshape(-1, self.P)
+        Tq = Phi.shape[0]
+        if Tq == 0:
+            raise ValueError("at least one query time")
+        with launch_stream(stream, self.device, (self._built,)) as (s, cur):
+            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
+            Rw_t, rstr = self._rw(Rw, B)
+            PhiQ = _dev(Phi, self.device)
+            n, P, M = self.n, self.P, self.M
+            cov = torch.empty((B, Tq, n, n), dtype=torch.float64, device=self.device)
+            status = torch.empty(B, dtype=torch.int32, device=self.device)
+            # the large-system workspace and the query columns' scratch are streamed in
+            # chunks like solve()'s, the outputs written in place at each chunk's offset
+            chunk = max(1, self._chunk(B, s))
+            ws, nb = self._workspace(chunk, s)
+            sb = self.lib.mhe_cov_scratch_bytes(self.dims, chunk, Tq)
+            scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
+            for lo in range(0, B, chunk):
+                a = _lib.MheSolveArgs()
+                a.batch = min(chunk, B - lo)
+                a.X0 = _at(X, lo, P * n)
+                a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
+                a.Y = _at(Y_t, lo, M * self.p)
+                a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
+                a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
+                a.x0 = _at(x0_t, lo, n)
+                a.workspace, a.workspace_bytes = _ptr(ws), nb
+                rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
+                                            _at(cov, lo, Tq * n * n), _at(status, lo, 1, 4), _ptr(scratch), sb,
+                                            _handle(s))
+                _lib.check(rc, "mhe_state_cov")
+            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, x0_t, PhiQ, cov, status, ws, scratch)
+        return cov, status
+
     def chol_solve(self, H, g, stream=None):
         """delta = -H^{-1} g with the solver's own factorization (H: (B,dp,dp) SPD,
         node-major as ``assemble`` returns it; lower triangle read): the register-tiled

@@ -709,6 +709,7 @@ class fixedTimeOptimalEstimationNLP(NLP):
             lam_t = torch.empty((1, eng.n_eq), dtype=torch.float64, device=eng.device)
         out = eng.solve(X0, U, Y, PAR, x0, max_iter=self.max_iter, tol=self.tol, Z0=Z0, Rw=Rw, lam_out=lam_t)
         X, cost, iters, status = out[:4]
+        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, engine=eng)  # extractCovariance
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         X = X.cpu().numpy()[0]
@@ -733,6 +734,35 @@ class fixedTimeOptimalEstimationNLP(NLP):
         if st != 0 and not _quiet:
             warnings.warn(f"Gauss-Newton solve ended with {statuses[st]}")
         return lam_t
+
+    def extractCovariance(self, name, t_array):
+        """Posterior covariance (T, n, n) of the last solve's state estimate at the times
+        ``t_array`` -- what extractSolution returns the mean of: S_t (J^T W J)^-1 S_t^T at
+        the solution, with that solve's controls, measurements, prior and R
+        (BatchSolver.covariance).  A covariance when Q, R and the prior weight are inverse
+        covariances; e.g. ``inv(extractCovariance("x", [DT])[0])`` is the arrival-cost weight
+        of the next window.  State bounds are not reflected.  Raises UnsupportedFeature for
+        problems with mixed rows / extra variables, constraints (a covariance under
+        constraints is a projected quantity), for a variable other than the state
+        trajectory, and before the first solve()."""
+        last = getattr(self, "_last_solve", None)
+        if self.sol is None or last is None:
+            raise UnsupportedFeature("extractCovariance needs a solve() first")
+        if self._X is None or name != self._X[0].name:
+            raise UnsupportedFeature(f"extractCovariance: {name!r} is not the state trajectory")
+        eng = last["engine"]  # the engine of that solve (a re-set R or prior may have built another since)
+        if self._ineq or self._eq or self._active or eng.n_eq or eng.n_extra or eng.meas_name == "mixed":
+            raise UnsupportedFeature("extractCovariance: general (mixed-row), active-set and bordered problems "
+                                     "have no unconstrained covariance")
+        import torch
+        X = np.stack([x.value for x in self._X])[None]
+        Phi = self.CPM.lagrange_matrix(np.asarray(t_array, dtype=np.float64).reshape(-1))
+        cov, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"])
+        torch.cuda.synchronize()
+        st = int(status.cpu().numpy()[0])
+        if st != 0:
+            warnings.warn(f"extractCovariance: the normal matrix at the solution is not usable (status {st})")
+        return cov.cpu().numpy()[0]
 
     def _check_bounds(self):
         viol = False

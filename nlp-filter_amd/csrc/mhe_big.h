@@ -26,30 +26,10 @@
 // Converged or failed trajectories are frozen by a per-trajectory state word,
 // so the host loop only enqueues (no synchronisation).
 
-#ifndef MHE_BIG_DIAG_DB
-#define MHE_BIG_DIAG_DB 1  // split diagonal stage: KC = 2 double-buffered slabs (C3 +0.8 %, C4 0)
-#endif
-#ifndef MHE_BIG_ENV
-#define MHE_BIG_ENV 1  // split form: skip the tiles outside the factor's envelope (component-pair sparsity; C5 5.8x, C3 +8 %)
-#endif
-#ifndef MHE_BIG_WSKIP
-#define MHE_BIG_WSKIP 1  // envelope: a row's wave skips the left-looking chunks left of its own f (k_big_rows: C5 +2.5 %, C3 +2.7 %)
-#endif
-#ifndef MHE_BIG_WSKIP_DIAG
-#define MHE_BIG_WSKIP_DIAG 0  // the same for the diagonal stage's rows (neutral to -1 %; with the rows' skip C4 -4 %)
-#endif
-#ifndef MHE_BIG_ASM_ZSKIP
-#define MHE_BIG_ASM_ZSKIP 1  // envelope: k_big_assemble skips storing zero tiles the previous factorization left zero (C5 +2.8 %)
-#endif
-#ifndef MHE_BIG_RESID_SLOTS
-#define MHE_BIG_RESID_SLOTS 1  // k_big_resid, mixed rows: per-slot gradients (MeasMixed::eval_slots), scratch 752 -> 352 B/lane (C5 +1.8 %)
-#endif
-#ifndef MHE_BIG_DIAG_AKPF
-#define MHE_BIG_DIAG_AKPF 1  // diagonal block: the next diagonal tile loaded one column ahead (+0.3 %)
-#endif
-#ifndef MHE_BIG_RESID_LDS
-#define MHE_BIG_RESID_LDS 1  // k_big_resid: X staged in LDS for the node / epoch dot products (C3 +0.7 %)
-#endif
+//
+// Each technique below was kept after a recorded A/B (profiles/r0*_ab_*.txt, DESIGN
+// §5/§9); the gain is noted where the code is.  The losing arms are not kept.
+
 constexpr int BIG_NW = 8;
 constexpr int BIG_NTHREADS = BIG_NW * 64;
 constexpr int BIG_RUNNING = -1;
@@ -331,13 +311,13 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
   const BigConst CL = big_const_layout(a.P, a.M, n, p, a.nc);
   const BigWs WL = big_ws_layout(a.P, a.M, n, a.NT, a.nz, a.nc);
   double* ws = a.ws + (size_t)b * a.ws_stride;
-  // MHE_BIG_ENV: which component pairs (a, b) have a nonzero block of H at this iterate --
+  // envelope: which component pairs (a, b) have a nonzero block of H at this iterate --
   // from the E, F^T E and G_e values formed below (one coalesced pass over each, flags in
   // LDS), Qw and Pw; k_big_assemble skips the others' epoch GEMM and writes their tiles as
-  // zeros, the split factorization derives its envelope from them
-  __shared__ int pflag[MHE_BIG_ENV ? n * n : 1];
-  if (MHE_BIG_ENV)
-    for (int t = threadIdx.x; t < n * n; t += BIG_NTHREADS) pflag[t] = 0;
+  // zeros, the split factorization derives its envelope from them (skipping the tiles
+  // outside the factor's envelope: C5 5.8x, C3 +8 %)
+  __shared__ int pflag[n * n];
+  for (int t = threadIdx.x; t < n * n; t += BIG_NTHREADS) pflag[t] = 0;
   const double* D = (const double*)(a.cbuf + CL.D);
   const double* Dt = (const double*)(a.cbuf + CL.Dt);
   const double* cw = (const double*)(a.cbuf + CL.cw);
@@ -349,15 +329,13 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
   const int* erow = (const int*)(a.cbuf + CL.erow);
   const int E = a.M > 0 ? *(const int*)(a.cbuf + CL.ne) : 0;
   const int Mr = a.M > 0 ? a.M : 1;
-  // X staged in LDS (MHE_BIG_RESID_LDS; dynamic LDS of P n doubles): every thread's node
-  // and epoch dot products read all of X, as LDS broadcasts instead of L1/L2 loads
+  // X staged in LDS (dynamic LDS of P n doubles): every thread's node and epoch dot
+  // products read all of X, as LDS broadcasts instead of L1/L2 loads (C3 +0.7 %)
   extern __shared__ __attribute__((aligned(16))) double xl_dyn[];
   const double* Xg = a.X + (size_t)b * a.P * n;
-  if (MHE_BIG_RESID_LDS) {
-    for (int t = threadIdx.x; t < a.P * n; t += BIG_NTHREADS) xl_dyn[t] = Xg[t];
-    __syncthreads();
-  }
-  const double* X = MHE_BIG_RESID_LDS ? xl_dyn : Xg;
+  for (int t = threadIdx.x; t < a.P * n; t += BIG_NTHREADS) xl_dyn[t] = Xg[t];
+  __syncthreads();
+  const double* X = xl_dyn;
   __shared__ double red[2 * BIG_NW];
   double cost = 0.0, noise = 0.0;  // noise: the cost's rounding level (bounded problems' line search)
   // interpolated states at the epochs: x_e = sum_j Phi_E[e][j] X_j
@@ -441,7 +419,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
     // accumulated per epoch for k_big_border.  A row's gradient has at most 8 nonzeros
     // (MHE_ROW_* codes), so its outer product is scattered straight into the epoch's
     // blocks in the workspace (no n x n private array: n = 40 for the 8-receiver C5)
-    constexpr int NA = MEAS::NA, NZX = MHE_MAX_EXTRA;
+    constexpr int NZX = MHE_MAX_EXTRA;
     const int nz = a.nz;
     for (int e = threadIdx.x; e < E; e += BIG_NTHREADS) {
       double* G = ws + WL.Ge + (size_t)e * n * n;
@@ -449,13 +427,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
       double* Gz = ws + WL.GZe + (size_t)e * n * NZX;
       double* Hzz = ws + WL.HZZe + (size_t)e * NZX * NZX;
       double* gz = ws + WL.GZVe + (size_t)e * NZX;
-      double xt[MHE_BIG_RESID_SLOTS ? 1 : NA];
-      for (int c = 0; c < n; ++c) {
-        if (!MHE_BIG_RESID_SLOTS) xt[c] = ws[WL.XE + e * n + c];
-        ge[c] = 0.0;
-      }
-      if (!MHE_BIG_RESID_SLOTS)
-        for (int c = 0; c < NZX; ++c) xt[n + c] = c < nz ? a.Z[(size_t)b * nz + c] : 0.0;
+      for (int c = 0; c < n; ++c) ge[c] = 0.0;
       for (int c = 0; c < n * n; ++c) G[c] = 0.0;
       if (nz > 0) {
         for (int c = 0; c < n * NZX; ++c) Gz[c] = 0.0;
@@ -466,64 +438,40 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
         const double* PR = a.PAR + (long long)b * a.pstride + (long long)i * q;
         const double R = Rw[i];
         if (R == 0.0) continue;  // R = 0 masks the row (empty satellite slot, autonomous-car.py:260-263)
-        if constexpr (MHE_BIG_RESID_SLOTS) {
-          // per-slot gradient: a component in two slots gets their sum (two terms: the same
-          // value as the dense accumulation), zero gradients dropped -- the dense form's
-          // nonzero set; each (ia, ib) entry is still added once per row, so G_e, g_e and
-          // the z blocks take the same values
-          double h, gs[7];
-          int id[7];
-          MEAS::eval_slots([&](int c) { return c < n ? ws[WL.XE + e * n + c] : a.Z[(size_t)b * nz + (c - n)]; }, PR, nz, h,
-                           id, gs);
+        // per-slot gradient: a component in two slots gets their sum (two terms: the same
+        // value as the dense accumulation), zero gradients dropped -- the dense form's
+        // nonzero set; each (ia, ib) entry is still added once per row, so G_e, g_e and
+        // the z blocks take the same values (scratch 752 -> 352 B/lane, C5 +1.8 %)
+        double h, gs[7];
+        int id[7];
+        MEAS::eval_slots([&](int c) { return c < n ? ws[WL.XE + e * n + c] : a.Z[(size_t)b * nz + (c - n)]; }, PR, nz, h,
+                         id, gs);
 #pragma unroll
-          for (int k1 = 0; k1 < 7; ++k1)
+        for (int k1 = 0; k1 < 7; ++k1)
 #pragma unroll
-            for (int k2 = k1 + 1; k2 < 7; ++k2)
-              if (id[k1] >= 0 && id[k2] == id[k1]) {
-                gs[k1] += gs[k2];
-                id[k2] = -1;
-              }
-#pragma unroll
-          for (int k1 = 0; k1 < 7; ++k1)
-            if (gs[k1] == 0.0) id[k1] = -1;
-          const double yv = a.Y[(long long)b * a.M + i], ev = yv - h, Re = R * ev;
-          cost += ev * Re;
-          noise += fabs(Re) * (fabs(yv) + fabs(h));
-#pragma unroll
-          for (int u = 0; u < 7; ++u) {
-            if (id[u] < 0) continue;
-            const int ia = id[u];
-            const double ga = gs[u];
-            if (ia < n) ge[ia] += ga * Re;
-            else gz[ia - n] += ga * Re;
-#pragma unroll
-            for (int v = 0; v < 7; ++v) {
-              if (id[v] < 0) continue;
-              const int ib = id[v];
-              const double w2 = ga * R * gs[v];
-              if (ia < n && ib < n) G[ia * n + ib] += w2;
-              else if (ia < n) Gz[ia * NZX + (ib - n)] += w2;
-              else if (ib >= n) Hzz[(ia - n) * NZX + (ib - n)] += w2;
+          for (int k2 = k1 + 1; k2 < 7; ++k2)
+            if (id[k1] >= 0 && id[k2] == id[k1]) {
+              gs[k1] += gs[k2];
+              id[k2] = -1;
             }
-          }
-          continue;
-        }
-        double h, Gr[NA];
-        MEAS::eval(xt, PR, nz, h, Gr);
+#pragma unroll
+        for (int k1 = 0; k1 < 7; ++k1)
+          if (gs[k1] == 0.0) id[k1] = -1;
         const double yv = a.Y[(long long)b * a.M + i], ev = yv - h, Re = R * ev;
         cost += ev * Re;
         noise += fabs(Re) * (fabs(yv) + fabs(h));
-        int id[8], k = 0;
-        for (int c = 0; c < NA && k < 8; ++c)
-          if (Gr[c] != 0.0) id[k++] = c;
-        for (int u = 0; u < k; ++u) {
+#pragma unroll
+        for (int u = 0; u < 7; ++u) {
+          if (id[u] < 0) continue;
           const int ia = id[u];
-          const double ga = Gr[ia];
+          const double ga = gs[u];
           if (ia < n) ge[ia] += ga * Re;
           else gz[ia - n] += ga * Re;
-          for (int v = 0; v < k; ++v) {
+#pragma unroll
+          for (int v = 0; v < 7; ++v) {
+            if (id[v] < 0) continue;
             const int ib = id[v];
-            const double w2 = ga * R * Gr[ib];
+            const double w2 = ga * R * gs[v];
             if (ia < n && ib < n) G[ia * n + ib] += w2;
             else if (ia < n) Gz[ia * NZX + (ib - n)] += w2;
             else if (ib >= n) Hzz[(ia - n) * NZX + (ib - n)] += w2;
@@ -623,7 +571,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
     a.cost[b] = c;
     if (a.n_bounds > 0) ws[WL.NZ] = COST_NOISE * __DBL_EPSILON__ * z;
   }
-  if (MHE_BIG_ENV && !final_pass) {
+  if (!final_pass) {
     // (the barrier above ordered every thread's E, F^T E and G_e writes before these reads)
     const size_t nes = (size_t)n * n * a.P, nge = (size_t)E * n * n;
     for (size_t t = threadIdx.x; t < nes; t += BIG_NTHREADS) {
@@ -766,19 +714,19 @@ __global__ __launch_bounds__(256, 4) void k_big_assemble(BigArgs a) {
   const bool live = valid && ch < a.nchl;
   const int q0 = !valid ? 0 : live ? ch * a.pchl : a.nlive + (ch - a.nchl) * BIG_PCH;
   const int np = !valid ? 0 : min(live ? a.pchl : BIG_PCH, (live ? a.nlive : a.npr) - q0);
-  // MHE_BIG_ENV: bit q set when pair q's block of H can be nonzero at this iterate (k_big_resid's
+  // envelope: bit q set when pair q's block of H can be nonzero at this iterate (k_big_resid's
   // flags); the others skip the epoch GEMM (their G_e are zero) and write zero tiles
   int lqm = 0;
 #pragma unroll
   for (int q = 0; q < BIG_PCH; ++q)
-    if (q < np && (!MHE_BIG_ENV || big_env_mask(ws, WL)[a.pa[q0 + q] * n + a.pb[q0 + q]] != 0)) lqm |= 1 << q;
+    if (q < np && big_env_mask(ws, WL)[a.pa[q0 + q] * n + a.pb[q0 + q]] != 0) lqm |= 1 << q;
   d4 acc[BIG_PCH];
 #pragma unroll
   for (int q = 0; q < BIG_PCH; ++q) acc[q] = d4{0.0, 0.0, 0.0, 0.0};
   const double* Ge = ws + WL.Ge;
-  // workgroup-uniform; MHE_BIG_ENV: a workgroup none of whose pairs has a nonzero term
+  // workgroup-uniform; envelope: a workgroup none of whose pairs has a nonzero term
   // skips the whole epoch loop (its staging and barriers, not only the MFMAs)
-  if (gblock && E > 0 && (!MHE_BIG_ENV || __syncthreads_or(lqm != 0))) {
+  if (gblock && E > 0 && __syncthreads_or(lqm != 0)) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int KC = BIG_AKC, SA = KC * 16, SGW = BIG_PCH * KC;
     const int SBUF = 2 * SA + WPB * SGW;
@@ -896,10 +844,10 @@ __global__ __launch_bounds__(256, 4) void k_big_assemble(BigArgs a) {
       // E_l[ca][cb] and E_j[cb][ca] (component-major: node index fastest)
       const int sE1 = (int)((WL.Es + (size_t)(ca * n + cb) * P) * 8), sE2 = (int)((WL.Es + (size_t)(cb * n + ca) * P) * 8);
       const int sF = (int)(WL.FtE * 8) + (ca * n + cb) * 8;
-      if (MHE_BIG_ASM_ZSKIP && !((lqm >> q) & 1)) {
+      if (!((lqm >> q) & 1)) {
         // a pair without a nonzero term: zero tiles, not stored where the previous
         // factorization's envelope already left zeros (a tile left of its row's f: A was 0
-        // there, and the factorization wrote nothing but zeros left of f)
+        // there, and the factorization wrote nothing but zeros left of f; C5 +2.8 %)
         const int* FIp = big_env_first(ws, WL, n);
 #pragma unroll
         for (int tp = 0; tp < 2; ++tp) {
@@ -926,9 +874,7 @@ __global__ __launch_bounds__(256, 4) void k_big_assemble(BigArgs a) {
           const int tr = tp ? cc : cr, tc = tp ? cr : cc;       // position in the written tile
           const int j = 16 * ti + tr, l = 16 * tj + tc;
           double v;
-          if (!((lqm >> q) & 1)) {
-            v = 0.0;  // a pair without a nonzero term (never a diagonal pair: no identity padding)
-          } else if (j < P && l < P) {
+          if (j < P && l < P) {
             // every operand read along the lane-varying index (l for the tile, j for its
             // transpose): D_lj from D^T or D, D_jl from D or D^T, the exactly symmetric
             // D^T C D either way, E component-major -- coalesced, not P- or n^2-strided
@@ -978,76 +924,25 @@ constexpr int BIG_KB = 8;      // tile columns per super-block
 // 1 / JB.  JB = 8 (128 KB slab, one workgroup per CU) for wide systems (NT >=
 // BIG_WIDE_NT, C4: HBM-bound there), JB = 4 (64 KB, two workgroups per CU, whose
 // overlap the latency-bound panel phase of narrower systems needs) otherwise.
-#ifndef MHE_BIG_WIDE_NT
-#define MHE_BIG_WIDE_NT 128
-#endif
-constexpr int BIG_WIDE_NT = MHE_BIG_WIDE_NT;
-#ifndef MHE_BIG_LLR8
-#define MHE_BIG_LLR8 2  // rows per wave of the left-looking update, 8-wide slab instance
-#endif
-#ifndef MHE_BIG_SPLIT
-#define MHE_BIG_SPLIT 1  // the left-looking factorization as per-block-column launches (k_big_chol SPLIT,
-                         // k_big_rows): 1 = always (round 6: C3 too), 2 = for wide systems only (NT >=
-                         // BIG_WIDE_NT: C4, C5; the round-5 default), 0 = never
-#endif
-#ifndef MHE_BIG_TWO_STREAMS
-#define MHE_BIG_TWO_STREAMS 1  // split factorization: the batch's two halves on two streams (envelope build: C5 +6.2 %, C3 +1.5 %, C4 0)
-#endif
-#ifndef MHE_BIG_DIAG_REG
-#define MHE_BIG_DIAG_REG 1  // split diagonal stage: its rows' left-looking update register-resident (as k_big_rows)
-#endif
-#ifndef MHE_BIG_DIAG_SKIP
-#define MHE_BIG_DIAG_SKIP 1  // split diagonal stage: skip the MFMAs of tiles past a row's diagonal, SIMD-balanced rows
-#endif
-#ifndef MHE_BIG_DIAG_LROW
-#define MHE_BIG_DIAG_LROW 1  // split diagonal stage: the rows' own L_Ik from the staged slab (LDS), not HBM
-#endif
-#ifndef MHE_BIG_BWD_PF
-#define MHE_BIG_BWD_PF 2  // split solve launch: tiles of the next column each wave has in flight (5: slower at C3)
-#endif
-#ifndef MHE_BIG_ROWS_SKIP
-#define MHE_BIG_ROWS_SKIP 1  // k_big_rows: row-less waves skip the left-looking MFMAs
-#endif
-#ifndef MHE_BIG_BWD_COAL
-#define MHE_BIG_BWD_COAL 1  // backward solve: coalesced tile loads, one DPP row reduction per step (C3 +3.7 %, C4 +2.1 %)
-#endif
-#ifndef MHE_BIG_ROWS_TLDS
-#define MHE_BIG_ROWS_TLDS 1  // k_big_rows: the row's A_Ik^T read coalesced and transposed through LDS (C3 +1.8 %, C4 +1.1 %)
-#endif
-#ifndef MHE_BIG_ROWS_LBDMA
-#define MHE_BIG_ROWS_LBDMA 1  // k_big_rows: the in-block L tiles and L_kk^-T staged by LDS-DMA (C3 +2.4 %, C4 0)
-#endif
-#ifndef MHE_BIG_ROWS_KC
-#define MHE_BIG_ROWS_KC 2  // k_big_rows: k tiles per staged slab
-#endif
-#ifndef MHE_BIG_ROWS_DB
-#define MHE_BIG_ROWS_DB 1  // k_big_rows: slabs double-buffered (the next in flight during this one's MFMAs)
-#endif
-#ifndef MHE_BIG_ROWS_RPF
-#define MHE_BIG_ROWS_RPF 1  // k_big_rows: the row's L_Ik loaded a whole slab chunk ahead
-#endif
-#ifndef MHE_BIG_ROWS_XCD
-#define MHE_BIG_ROWS_XCD 1  // k_big_rows: a trajectory's row groups on one XCD (batch % 8 == 0)
-#endif
+constexpr int BIG_WIDE_NT = 128;
+constexpr int BIG_BWD_PF = 2;   // split solve launch: tiles of the next column each wave has in flight (5: slower at C3)
+constexpr int BIG_ROWS_KC = 2;  // k_big_rows: k tiles per staged slab
 #ifndef MHE_BIG_KO
 #define MHE_BIG_KO 0  // knock-out mask for timing probes only (tools/ko_big.sh): 1 trailing / left-looking
-                      // update, 2 in-block, 4 TRSM, 8 the left-looking update's slab staging,
-                      // 16 the rows below the diagonal block, 32 the backward solve; any
+                      // update, 2 in-block, 4 TRSM, (8 was the one-launch left-looking form's slab
+                      // staging: no effect now), 16 the rows below the diagonal block (right-
+                      // looking form), 32 the backward solve; any
                       // nonzero mask also freezes X (k_big_update), 64 only that (the baseline)
 #endif
-#ifndef MHE_BIG_HEAD
-#define MHE_BIG_HEAD 1  // split form: the NT % 8 leftover tile columns as the FIRST block column, so every
-                        // rows launch has whole groups of 8 rows (C3: NT = 65; +9.8 %)
-#endif
 constexpr int BIG_LB_TILES = BIG_KB * (BIG_KB - 1) / 2;
-// End of the split form's block column that starts at k0.  Block columns are 8 wide; with
-// MHE_BIG_HEAD the NT % 8 leftover columns form the first one instead of the last, so the
+// End of the split form's block column that starts at k0.  Block columns are 8 wide; the
+// NT % 8 leftover columns form the FIRST one (the "head") instead of the last, so the
 // rows below every block column are a multiple of 8 (k_big_rows: one workgroup per 8 rows;
 // at C3, NT = 65, a trailing 1-wide block left one row in the last group of EVERY rows
-// launch).  Tile results do not depend on the partition: each tile's updates accumulate
-// in ascending k in every form.
+// launch: +9.8 %).  Tile results do not depend on the partition: each tile's updates
+// accumulate in ascending k in every form.
 __host__ __device__ inline int big_split_kend(int k0, int NT) {
-  const int h = MHE_BIG_HEAD ? NT % BIG_KB : 0;
+  const int h = NT % BIG_KB;
   return (k0 == 0 && h != 0) ? h : (k0 + BIG_KB < NT ? k0 + BIG_KB : NT);
 }
 // the LJ region: the trailing slab, or (panel phase) the in-block L tiles LB and the
@@ -1097,12 +992,12 @@ __device__ __forceinline__ void stage_slab_lds(double* LJ, const double* H, int 
   if (wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Block column k0 of the left-looking factorization up to its diagonal block: the
-// left-looking update of the column's tiles (rows < rowend: all rows in the one-launch
-// form, the block's own rows in the split one), then the diagonal block (panels on wave 0,
-// in-block updates and TRSM on the others; L_Ik to H and LB, L_kk^-T to LT and LTs, y_k to
-// YV, b_I updated).  LDS as k_big_chol's (DT, flag, UN, LJ); a non-SPD pivot sets *flag.
-template <int BIG_JB, bool LL, bool SPLITROWS, bool PREC = false>
+// Block column k0 up to its diagonal block: in the split (left-looking) form the
+// left-looking update of the block's own rows first, then in either form the diagonal
+// block (panels on wave 0, in-block updates and TRSM on the others; L_Ik to H and LB,
+// L_kk^-T to LT and LTs, y_k to YV, b_I updated).  LDS as k_big_chol's (DT, flag, UN, LJ);
+// a non-SPD pivot sets *flag.
+template <bool SPLITROWS, bool PREC = false>
 __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int kend, double* H, double* LTg, double* BV,
                                                double* YV, double* sm, int lane, int wave, const int* FI = nullptr) {
   double* DT = sm;
@@ -1110,32 +1005,30 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
   double* UN = sm + DTS + BIG_NW * 16 + 16 + 2;
   double* LJ = UN + UNITS;
   const int NT = a.NT;
-  if constexpr (LL && SPLITROWS && MHE_BIG_DIAG_REG) {
+  if constexpr (SPLITROWS) {
     // ---- split form: the left-looking update of the block's own <= 8 rows, one row per
-    // wave with its (up to 8) block-column tiles as accumulators, the kb x 4 slab of L_Jk
-    // staged by LDS-DMA and shared by the 8 rows -- as k_big_rows, but in the tiles' own
-    // orientation (the diagonal block below reads them from H).  Branch-free: tiles past
-    // the row's diagonal and waves without a row compute on clamped tiles, stores only.
-    // Same operations and order per element as the pass below.
-    // MHE_BIG_DIAG_DB: KC = 2 slabs double-buffered (the next chunk's LDS-DMA in flight
-    // during this one's MFMAs; 2 x 32 KB in the LJ region), else KC = 4 single-buffered
-    constexpr bool DDB = MHE_BIG_DIAG_DB != 0;
-    constexpr int KC = DDB ? 2 : 4;
+    // wave with its (up to 8) block-column tiles as accumulators (register-resident, as
+    // k_big_rows), the kb x KC slab of L_Jk staged by LDS-DMA and shared by the 8 rows --
+    // in the tiles' own orientation (the diagonal block below reads them from H).  Each
+    // tile's updates accumulate in ascending k, as in every form.
+    // KC = 2 slabs double-buffered: the next chunk's LDS-DMA in flight during this one's
+    // MFMAs; 2 x 32 KB in the LJ region (C3 +0.8 %, C4 0)
+    constexpr int KC = 2;
     constexpr int SLABD = BIG_KB * KC * 256;
-    static_assert(!DDB || 2 * SLABD <= BIG_LB_TILES * 256 + BIG_KB * DTS, "both slabs fit the LJ region");
-    static_assert(!MHE_BIG_HEAD || KC <= 2, "k0 need not be a multiple of KC: a chunk's tiles must stay below the diagonal");
+    static_assert(2 * SLABD <= BIG_LB_TILES * 256 + BIG_KB * DTS, "both slabs fit the LJ region");
+    static_assert(KC <= 2, "k0 need not be a multiple of KC (head block): a chunk's tiles must stay below the diagonal");
     const int kb = kend - k0;
     if (k0 > 0 && !(MHE_BIG_KO & 1)) {
       const int wv = __builtin_amdgcn_readfirstlane(wave);
       // Row k0 + o needs only its o + 1 tiles up to the diagonal: the MFMAs of tiles past it
-      // (and every MFMA of a wave without a row) are skipped by wave-uniform branches
-      // (MHE_BIG_DIAG_SKIP), and the rows are dealt so that the two waves sharing a SIMD
+      // (and every MFMA of a wave without a row) are skipped by wave-uniform branches,
+      // and the rows are dealt so that the two waves sharing a SIMD
       // (w, w + 4) take rows o and 7 - o: 9 tiles per SIMD instead of up to 16.
-      const int o = (MHE_BIG_DIAG_SKIP && wv >= 4) ? 11 - wv : wv;
+      const int o = wv >= 4 ? 11 - wv : wv;
       const int I = k0 + o;
       const bool act = I < kend;
       const int Ic = act ? I : kend - 1, jlast = Ic - k0;
-      const int jdo = MHE_BIG_DIAG_SKIP ? (act ? jlast : -1) : BIG_KB - 1;  // last tile computed
+      const int jdo = act ? jlast : -1;  // last tile computed
       d4 acc[BIG_KB];
 #pragma unroll
       for (int jj = 0; jj < BIG_KB; ++jj) {
@@ -1143,40 +1036,33 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[jj][r] = C[64 * r + lane];
       }
-      // MHE_BIG_ENV: the update starts at the block rows' first nonzero tile column (their
+      // envelope: the update starts at the block rows' first nonzero tile column (their
       // L_Jk left of it are zero), rounded down to a chunk
       int kst = 0;
-      if (MHE_BIG_ENV && FI) {
+      if (FI) {
         kst = k0;
         for (int J = k0; J < kend; ++J) kst = min(kst, FI[J]);
         kst &= ~(KC - 1);
       }
-      if (DDB && kst < k0) stage_slab_lds(LJ, H, k0, kb, kst, KC, NT, false);
+      if (kst < k0) stage_slab_lds(LJ, H, k0, kb, kst, KC, NT, false);  // L_Jk, J = k0 + jj, k = kst + kk
       for (int kc = kst; kc < k0; kc += KC) {
         const int ci = (kc - kst) / KC;  // chunk index: slab buffer ci & 1
-        double* S = LJ + (DDB ? (ci & 1) * SLABD : 0);
-        if (DDB) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this chunk's slab has landed
-          __syncthreads();  // ... for every wave; the other buffer's readers are done
-          if (kc + KC < k0) stage_slab_lds(LJ + ((ci + 1) & 1) * SLABD, H, k0, kb, kc + KC, KC, NT, false);
-        } else {
-          __syncthreads();  // the previous slab is consumed
-          stage_slab_lds(LJ, H, k0, kb, kc, KC, NT);  // L_Jk, J = k0 + jj, k = kc + kk
-          __syncthreads();
-        }
-        if (MHE_BIG_WSKIP_DIAG && FI && act && kc + KC <= FI[Ic]) continue;  // the row's L_Ik here are zero
+        double* S = LJ + (ci & 1) * SLABD;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this chunk's slab has landed
+        __syncthreads();  // ... for every wave; the other buffer's readers are done
+        if (kc + KC < k0) stage_slab_lds(LJ + ((ci + 1) & 1) * SLABD, H, k0, kb, kc + KC, KC, NT, false);
+        // (skipping the chunks left of the row's own first nonzero column, as k_big_rows
+        // does, lost here: neutral to -1 %, C4 -4 %)
         // the row's own L_Ik are slab tiles too (I is one of the block's rows J): read from
-        // LDS (MHE_BIG_DIAG_LROW) instead of a second time from HBM
-        auto lrow = [&](int kk) {
-          return MHE_BIG_DIAG_LROW ? S + (jlast * KC + kk) * 256 : H + (size_t)big_tile_index(Ic, kc + kk, NT) * 256;
-        };
+        // LDS instead of a second time from HBM
+        auto lrow = [&](int kk) { return S + (jlast * KC + kk) * 256; };
         double an[4];
         const double* L0 = lrow(0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) an[r] = L0[64 * r + lane];
 #pragma unroll
         for (int kk = 0; kk < KC; ++kk) {
-          if (MHE_BIG_HEAD && kc + kk >= k0) break;  // k0 odd (MHE_BIG_HEAD): the chunk's last tile is past it
+          if (kc + kk >= k0) break;  // k0 odd (head block): the chunk's last tile is past it
           double av[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) av[r] = an[r];  // negated by the MFMA
@@ -1206,98 +1092,6 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
       }
     }
     __syncthreads();  // the block column's tiles are up to date; LJ is free for LB / LTs
-  } else if constexpr (LL) {
-    // ---- left-looking update of block column k0 by all previous columns: a wave
-    // takes LLR rows (g0 + wave + 8 q), so one staged slab serves 8 LLR rows
-    constexpr int LLR = BIG_JB == 8 ? MHE_BIG_LLR8 : 2;
-    for (int jh = 0; jh < kend - k0 && k0 > 0 && !(MHE_BIG_KO & 1); jh += BIG_JB) {
-      const int jw = min(BIG_JB, kend - k0 - jh), Jb = k0 + jh;
-      const int rowend = SPLITROWS ? kend : NT;  // split: the rows below get theirs in k_big_rows
-      for (int g0 = Jb; g0 < rowend; g0 += BIG_NW * LLR) {
-        int Iq[LLR], jm[LLR];
-        d4 c[LLR][BIG_JB];
-#pragma unroll
-        for (int q = 0; q < LLR; ++q) {
-          Iq[q] = g0 + wave + BIG_NW * q;
-          jm[q] = Iq[q] < rowend ? min(jw, Iq[q] - Jb + 1) : 0;
-#pragma unroll
-          for (int jj = 0; jj < BIG_JB; ++jj) {
-            if (jj < jm[q]) {
-              const double* C = H + (size_t)big_tile_index(Iq[q], Jb + jj, NT) * 256;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) c[q][jj][r] = C[64 * r + lane];
-            }
-          }
-        }
-        for (int kc = 0; kc < k0; kc += BIG_KB) {
-          __syncthreads();  // the previous chunk's slab is consumed
-          if (!(MHE_BIG_KO & 8)) stage_slab(LJ, H, Jb, jw, kc, BIG_KB, NT);  // L_Jk, jj < jw, kk < BIG_KB
-          __syncthreads();
-          // both rows share each staged B operand (one LDS read per 2 x 4 MFMAs); the
-          // rows' next L_Ik tiles are loaded one k step ahead
-          double av[LLR][4];
-#pragma unroll
-          for (int q = 0; q < LLR; ++q) {
-            const double* LI0 = H + (size_t)big_tile_index(jm[q] > 0 ? Iq[q] : Jb, kc, NT) * 256;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) av[q][r] = LI0[64 * r + lane];  // negated by the MFMA
-          }
-#pragma unroll 1
-          for (int kk = 0; kk < BIG_KB; ++kk) {
-            double an[LLR][4];
-#pragma unroll
-            for (int q = 0; q < LLR; ++q) {
-              const double* LIn =
-                  H + (size_t)big_tile_index(jm[q] > 0 ? Iq[q] : Jb, kc + min(kk + 1, BIG_KB - 1), NT) * 256;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) an[q][r] = LIn[64 * r + lane];
-            }
-#pragma unroll
-            for (int jj = 0; jj < BIG_JB; ++jj) {
-              if (jj < jm[0]) {  // rows ascend with q: jm[0] <= jm[1]
-                const double* Bt = LJ + (jj * BIG_KB + kk) * 256;
-                double bv[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bv[r] = Bt[64 * r + lane];
-#pragma unroll
-                for (int q = 0; q < LLR; ++q) {
-                  if (jj < jm[q]) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                      c[q][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q][r], bv[r], c[q][jj], 0, 0, MFMA_NEG_A);
-                  }
-                }
-              } else if (jj < jm[LLR - 1]) {
-                const double* Bt = LJ + (jj * BIG_KB + kk) * 256;
-                double bv[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bv[r] = Bt[64 * r + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                  c[LLR - 1][jj] =
-                      __builtin_amdgcn_mfma_f64_16x16x4f64(av[LLR - 1][r], bv[r], c[LLR - 1][jj], 0, 0, MFMA_NEG_A);
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < LLR; ++q)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) av[q][r] = an[q][r];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < LLR; ++q) {
-#pragma unroll
-          for (int jj = 0; jj < BIG_JB; ++jj) {
-            if (jj < jm[q]) {
-              double* C = H + (size_t)big_tile_index(Iq[q], Jb + jj, NT) * 256;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) C[64 * r + lane] = c[q][jj][r];
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();  // the block column is up to date; LJ is free for LB / LTs
   }
   // ---- diagonal block, left-looking inside the block column: at step k every tile
   // (I, k), k <= I < kend, gets all of its in-block updates in ONE pass (K = 16 (k - k0),
@@ -1306,10 +1100,10 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
   // strictly-lower: slot (I - k0)(I - k0 - 1)/2 + (k' - k0); LTs: L_kk^-T of the block's k.
   double* LB = LJ;
   double* LTs = LJ + BIG_LB_TILES * 256;
-  // wave 0's next diagonal tile is loaded one column ahead (MHE_BIG_DIAG_AKPF): A_kk is not
-  // written in the column loop before its own column, so its load latency leaves the chain
+  // wave 0's next diagonal tile is loaded one column ahead: A_kk is not written in the
+  // column loop before its own column, so its load latency leaves the chain (+0.3 %)
   d4 akn;
-  if (MHE_BIG_DIAG_AKPF && wave == 0) {
+  if (wave == 0) {
     const double* A0 = H + (size_t)big_tile_index(k0, k0, NT) * 256;
 #pragma unroll
     for (int r = 0; r < 4; ++r) akn[r] = A0[64 * r + lane];
@@ -1318,18 +1112,11 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
     const int nk = k - k0;
     if (wave == 0) {
       // diagonal tile: A_kk - sum L_kk' L_kk'^T -> DT, panel, y_k
-      const double* Akk = H + (size_t)big_tile_index(k, k, NT) * 256;
-      d4 c;
-      if (MHE_BIG_DIAG_AKPF) {
-        c = akn;
-        if (k + 1 < kend) {
-          const double* An = H + (size_t)big_tile_index(k + 1, k + 1, NT) * 256;
+      d4 c = akn;
+      if (k + 1 < kend) {
+        const double* An = H + (size_t)big_tile_index(k + 1, k + 1, NT) * 256;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) akn[r] = An[64 * r + lane];
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = Akk[64 * r + lane];
+        for (int r = 0; r < 4; ++r) akn[r] = An[64 * r + lane];
       }
       for (int kk = 0; kk < nk && !(MHE_BIG_KO & 2); ++kk) {
         const double* Lt = LB + (nk * (nk - 1) / 2 + kk) * 256;
@@ -1402,19 +1189,22 @@ __device__ __forceinline__ void big_diag_block(const BigArgs& a, int k0, int ken
 
 // LL = true: LEFT-looking updates instead of the trailing update.  Before block column
 // k0 is factored, its tiles (I, k0 .. kend-1), I >= k0, receive all their updates
-// sum_{k < k0} L_Ik L_Jk^T in one visit: a wave keeps one row's BIG_JB accumulators in
-// registers while the block column's L_Jk are staged through LDS BIG_KB tile columns at
+// sum_{k < k0} L_Ik L_Jk^T in one visit: a wave keeps one row's accumulators in
+// registers while the block column's L_Jk are staged through LDS a few tile columns at
 // a time.  Every tile is then read and written ONCE per factorization (the right-looking
 // update reads and writes it once per super-block above it); L_Ik is read once per block
 // column (as before) and the staged L_Jk once per group of 8 rows.
-// SPLIT (left-looking only) runs the factorization as one launch per stage instead of one
-// per trajectory: SPLIT = 1 is block column kfirst's diagonal stage (the left-looking update
-// of the block's own rows, then the diagonal block), k_big_rows the rows below it (a launch
-// of its own, one workgroup per 8 rows), SPLIT = 2 the backward solve.  SPLIT = 0: the whole
-// factorization and solve in one launch (the right-looking form, and the A/B baseline).
+// The left-looking factorization is always SPLIT: one launch per stage instead of one per
+// trajectory.  SPLIT = 1 is block column kfirst's diagonal stage (the left-looking update
+// of the block's own rows, then the diagonal block; the 4-wide instance only), k_big_rows
+// the rows below it (a launch of its own, one workgroup per 8 rows), SPLIT = 2 the backward
+// solve.  SPLIT = 0 (LL = false): the whole right-looking factorization and solve in one
+// launch (MHE_OPT_BIG_RIGHT_LOOKING).
 template <int BIG_JB, bool LL = false, int SPLIT = 0, bool PREC = false>
 __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(BigArgs a, int kfirst) {
   static_assert(SPLIT == 0 || LL, "the split stages are the left-looking factorization's");
+  static_assert(!(LL && SPLIT == 0), "the left-looking factorization exists only in its split form");
+  static_assert(!(SPLIT == 1 && BIG_JB == 8), "the diagonal stage has one (4-wide) instance");
   const int b = blockIdx.x;
   if (a.state[b] != BIG_RUNNING) return;
   const BigWs WL = big_ws_layout(a.P, a.M, a.n, a.NT, a.nz, a.nc);
@@ -1434,11 +1224,11 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
   const int NT = a.NT;
   if (threadIdx.x == 0) *flag = 0;
   init_units(UN);
-  // MHE_BIG_ENV: each tile row's first nonzero tile column from k_big_assemble's component-pair
+  // envelope: each tile row's first nonzero tile column from k_big_assemble's component-pair
   // flags, once per factorization (the first diagonal stage; read by the later stages)
-  int* FIw = MHE_BIG_ENV && SPLIT != 0 ? big_env_first(ws, WL, a.n) : nullptr;
+  int* FIw = SPLIT != 0 ? big_env_first(ws, WL, a.n) : nullptr;
   const int* FI = FIw;
-  if constexpr (MHE_BIG_ENV && SPLIT == 1) {
+  if constexpr (SPLIT == 1) {
     if (kfirst == 0) {
       const int* EM = big_env_mask(ws, WL);
       for (int t = threadIdx.x; t < NT; t += BIG_NTHREADS) {
@@ -1457,7 +1247,7 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
   const int kbeg = SPLIT == 1 ? kfirst : 0, kstop = SPLIT == 1 ? big_split_kend(kfirst, NT) : (SPLIT == 2 ? 0 : NT);
   for (int k0 = kbeg; k0 < kstop; k0 += BIG_KB) {
     const int kend = SPLIT == 1 ? kstop : min(k0 + BIG_KB, NT);
-    big_diag_block<BIG_JB, LL, SPLIT != 0, PREC>(a, k0, kend, H, LTg, BV, YV, sm, lane, wave, FI);
+    big_diag_block<SPLIT != 0, PREC>(a, k0, kend, H, LTg, BV, YV, sm, lane, wave, FI);
     double* LB = LJ;  // the diagonal block's L_Ik' and L_kk^-T (big_diag_block)
     double* LTs = LJ + BIG_LB_TILES * 256;
     if (*flag) break;
@@ -1624,8 +1414,8 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
   // when they fit, the global YV copy is written alongside for k_big_update.
   // the split form's solve launch (SPLIT = 2) runs nothing else, so its registers can hold
   // a whole column's tiles for this wave at C3 (NT = 65: <= 8 per wave) -- every tile of
-  // column k - 1 in flight during step k instead of two (MHE_BIG_BWD_PF)
-  constexpr int BWD_PF = SPLIT == 2 ? MHE_BIG_BWD_PF : (BIG_JB == 8 ? 4 : 2);
+  // column k - 1 in flight during step k instead of two (BIG_BWD_PF)
+  constexpr int BWD_PF = SPLIT == 2 ? BIG_BWD_PF : (BIG_JB == 8 ? 4 : 2);
   const bool yl = NT * 16 <= big_slab_doubles(BIG_JB);
   double* yb = yl ? LJ : YV;
   if (yl) {
@@ -1638,14 +1428,14 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
 #pragma unroll
     for (int m = 0; m < BWD_PF; ++m) {
       const int I = k + 1 + wave + BIG_NW * m;
-      if (I < NT && FI && FI[I] > k) {  // outside the envelope (MHE_BIG_ENV): L_Ik = 0, not read
+      if (I < NT && FI && FI[I] > k) {  // outside the envelope: L_Ik = 0, not read
 #pragma unroll
         for (int r = 0; r < 4; ++r) dst[m][r] = 0.0;
       } else if (I < NT) {
         const double* L = H + (size_t)big_tile_index(I, k, NT) * 256;
 #pragma unroll
         for (int r = 0; r < 4; ++r)  // L_Ik[tr][bc], k-major tile; coalesced: element (4r + bg) * 16 + bc
-          dst[m][r] = MHE_BIG_BWD_COAL ? L[64 * r + lane] : L[bc * 16 + bg + 4 * r];
+          dst[m][r] = L[64 * r + lane];
       }
     }
     if (wave == 0) {
@@ -1656,45 +1446,29 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
   if (!(MHE_BIG_KO & 32)) load_col(NT - 1, cur, lt);
   for (int k = NT - 1; k >= 0 && !(MHE_BIG_KO & 32); --k) {
     if (k > 0) load_col(k - 1, nxt, ltn);  // in flight during this step
-    double pv = 0.0;
-    double pq[4] = {0.0, 0.0, 0.0, 0.0};  // MHE_BIG_BWD_COAL: output column 4r + bg, this lane's row bc
+    // coalesced tile loads, one DPP row reduction per step (C3 +3.7 %, C4 +2.1 %)
+    double pq[4] = {0.0, 0.0, 0.0, 0.0};  // output column 4r + bg, this lane's row bc
 #pragma unroll
     for (int m = 0; m < BWD_PF; ++m) {
       const int I = k + 1 + wave + BIG_NW * m;
       if (I < NT) {
-        if (MHE_BIG_BWD_COAL) {
-          const double dI = yb[16 * I + bc];
+        const double dI = yb[16 * I + bc];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) pq[r] += cur[m][r] * dI;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) pv += cur[m][r] * yb[16 * I + bg + 4 * r];
-        }
+        for (int r = 0; r < 4; ++r) pq[r] += cur[m][r] * dI;
       }
     }
     for (int I = k + 1 + wave + BIG_NW * BWD_PF; I < NT; I += BIG_NW) {  // past the prefetched tiles (C4, C5)
       // (issuing these loads four at a time measured slower: the solve launch 1.23 -> 1.45 ms at C3)
       if (FI && FI[I] > k) continue;  // outside the envelope
       const double* L = H + (size_t)big_tile_index(I, k, NT) * 256;
-      if (MHE_BIG_BWD_COAL) {
-        const double dI = yb[16 * I + bc];
+      const double dI = yb[16 * I + bc];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pq[r] += L[64 * r + lane] * dI;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pv += L[bc * 16 + bg + 4 * r] * yb[16 * I + bg + 4 * r];
-      }
+      for (int r = 0; r < 4; ++r) pq[r] += L[64 * r + lane] * dI;
     }
-    if (MHE_BIG_BWD_COAL) {
-      // the 16 rows of each output column are the 16 lanes of a DPP row: lane (bc, bg) ends
-      // with column 4 r(bc) + bg, r(bc) = 2 (bc >> 3) + ((bc >> 2) & 1)
-      const double z = row16_sum4(pq, bc);
-      if ((bc & 3) == 0) PART[wave * 16 + 4 * (2 * (bc >> 3) + ((bc >> 2) & 1)) + bg] = z;
-    } else {
-      pv += __shfl_xor(pv, 16);
-      pv += __shfl_xor(pv, 32);
-      if (lane < 16) PART[wave * 16 + lane] = pv;
-    }
+    // the 16 rows of each output column are the 16 lanes of a DPP row: lane (bc, bg) ends
+    // with column 4 r(bc) + bg, r(bc) = 2 (bc >> 3) + ((bc >> 2) & 1)
+    const double z = row16_sum4(pq, bc);
+    if ((bc & 3) == 0) PART[wave * 16 + 4 * (2 * (bc >> 3) + ((bc >> 2) & 1)) + bg] = z;
     __syncthreads();
     if (wave == 0) {
       if (lane < 16) {
@@ -1730,8 +1504,7 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
 // accumulated transposed in registers, c^T = A_Ik^T - sum_{k<k0} L_Jk L_Ik^T (the staged
 // L_Jk as the MFMA A operand, the row's L_Ik streamed as B), then the in-block updates and
 // the TRSM run on those registers: every L_Ik (k < k0) is read once per block column and
-// L_Ik is written once.  Same operations in the same order per element as the one-launch
-// form's left-looking pass + rows pass.
+// L_Ik is written once.  Each tile's updates accumulate in ascending k, as in every form.
 //   staging  the kb x KC slab of L_Jk by LDS-DMA, double-buffered: chunk i + 1 is in flight
 //            while chunk i's MFMAs run (one barrier per chunk);
 //   XCD      a batch that is a multiple of 8 is remapped so all groups of a trajectory land
@@ -1741,11 +1514,11 @@ __global__ __launch_bounds__(BIG_NTHREADS, BIG_JB == 8 ? 2 : 4) void k_big_chol(
 __host__ __device__ constexpr int big_rows_lds() { return BIG_LB_TILES * 256 + BIG_KB * DTS; }  // doubles
 // One group of BIG_NW rows below block column k0 (rows kend + 8 grp + wave): the body of
 // k_big_rows.  sm: the LDS region of the slabs, LB and LTs (big_rows_lds() doubles).
-template <int KC, bool DB>
+template <int KC>
 __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, double* BV, const double* YV,
-                                               double* sm, int NT, int k0, int grp, const int* FI = nullptr) {
-  static_assert((DB ? 2 : 1) * BIG_KB * KC * 256 <= big_rows_lds(), "the slabs fit the LDS region");
-  static_assert(!MHE_BIG_HEAD || KC <= 2, "k0 need not be a multiple of KC: a chunk's tiles must stay below the diagonal");
+                                               double* sm, int NT, int k0, int grp, const int* FI) {
+  static_assert(2 * BIG_KB * KC * 256 <= big_rows_lds(), "both slabs fit the LDS region");
+  static_assert(KC <= 2, "k0 need not be a multiple of KC (head block): a chunk's tiles must stay below the diagonal");
   double* LB = sm;
   double* LTs = sm + BIG_LB_TILES * 256;
   const int kend = big_split_kend(k0, NT), kb = kend - k0;
@@ -1757,11 +1530,12 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
   const int I = kend + BIG_NW * grp + wave;
   const bool act = I < NT;
   const int Ic = act ? I : NT - 1;
-  // MHE_BIG_ENV: the group's left-looking update starts at its rows' first nonzero tile
+  // envelope: the group's left-looking update starts at its rows' first nonzero tile
   // column (rounded down to a chunk); a group whose rows are all zero in this block column
   // has nothing to do (its tiles hold A_Ik = 0 = L_Ik, and b_I -= L_Ik y_k is no change)
+  // (FI == nullptr: no envelope, every tile column from 0)
   int kst = 0;
-  if (MHE_BIG_ENV && FI) {
+  if (FI) {
     kst = NT;
     for (int w = 0; w < BIG_NW; ++w) {
       const int Iw = kend + BIG_NW * grp + w;
@@ -1770,40 +1544,31 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
     if (kst >= kend) return;
     kst = min(kst, k0) & ~(KC - 1);
   }
-  const int fI = (MHE_BIG_ENV && MHE_BIG_WSKIP && FI) ? FI[Ic] : 0;  // this wave's row's first nonzero tile column
+  // this wave's row's first nonzero tile column: the chunks left of it are skipped (C5 +2.5 %, C3 +2.7 %)
+  const int fI = FI ? FI[Ic] : 0;
   d4 acc[BIG_KB];
   constexpr int SLAB = BIG_KB * KC * 256;
-  if constexpr (MHE_BIG_ROWS_TLDS && DB) {
-    // A_Ik^T through LDS: the tiles read coalesced (element 64 r + lane = A[4r + g][c]), then
-    // transposed through this wave's padded 16 x 17 scratch in the second slab buffer (first
-    // staged at chunk 1, after a barrier) -- the per-lane transposed global reads touched 16
-    // cache lines per instruction
+  // A_Ik^T through LDS: the tiles read coalesced (element 64 r + lane = A[4r + g][c]), then
+  // transposed through this wave's padded 16 x 17 scratch in the second slab buffer (first
+  // staged at chunk 1, after a barrier) -- the per-lane transposed global reads touched 16
+  // cache lines per instruction (C3 +1.8 %, C4 +1.1 %)
 #pragma unroll
-    for (int kk = 0; kk < BIG_KB; ++kk) {
-      const double* A = H + (size_t)big_tile_index(Ic, k0 + min(kk, kb - 1), NT) * 256;
+  for (int kk = 0; kk < BIG_KB; ++kk) {
+    const double* A = H + (size_t)big_tile_index(Ic, k0 + min(kk, kb - 1), NT) * 256;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[kk][r] = A[64 * r + lane];
-    }
-    double* T = sm + SLAB + wave * 272;
+    for (int r = 0; r < 4; ++r) acc[kk][r] = A[64 * r + lane];
+  }
+  double* T = sm + SLAB + wave * 272;
 #pragma unroll
-    for (int kk = 0; kk < BIG_KB; ++kk) {
+  for (int kk = 0; kk < BIG_KB; ++kk) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) T[(4 * r + g) * 17 + c] = acc[kk][r];
-      wave_lds_sync();
+    for (int r = 0; r < 4; ++r) T[(4 * r + g) * 17 + c] = acc[kk][r];
+    wave_lds_sync();
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[kk][r] = T[c * 17 + g + 4 * r];  // A_Ik^T, k-major
-      wave_lds_sync();
-    }
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < BIG_KB; ++kk) {
-      const double* A = H + (size_t)big_tile_index(Ic, k0 + min(kk, kb - 1), NT) * 256;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[kk][r] = A[c * 16 + 4 * r + g];  // A_Ik^T, k-major
-    }
+    for (int r = 0; r < 4; ++r) acc[kk][r] = T[c * 17 + g + 4 * r];  // A_Ik^T, k-major
+    wave_lds_sync();
   }
   if (kst < k0 && !(MHE_BIG_KO & 1)) stage_slab_lds(sm, H, k0, kb, kst, KC, NT, false);
-#if MHE_BIG_ROWS_RPF
   // The row's L_Ik (B operands) a whole chunk ahead: tile kc + kk is loaded into bq[kk]
   // right after chunk kc - KC's MFMAs have read bq[kk], so its HBM latency is covered by
   // a chunk of MFMAs (and the slab wait) instead of by one k step.
@@ -1818,19 +1583,14 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
   }
   for (int kc = kst; kc < k0 && !(MHE_BIG_KO & 1); kc += KC) {
     const int ci = (kc - kst) / KC;  // chunk index: slab buffer ci & 1 (the first in buffer 0)
-    const double* LJ = sm + (DB ? (ci & 1) * SLAB : 0);
-    if (!DB && kc > kst) {
-      __syncthreads();  // the previous chunk's readers are done
-      stage_slab_lds(sm, H, k0, kb, kc, KC, NT, false);
-    }
+    const double* LJ = sm + (ci & 1) * SLAB;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this chunk's slab (and row tiles) have landed
-    __syncthreads();
-    if (DB && kc + KC < k0) stage_slab_lds(sm + ((ci + 1) & 1) * SLAB, H, k0, kb, kc + KC, KC, NT, false);
+    __syncthreads();  // ... for every wave, and the other buffer's last readers are done
+    if (kc + KC < k0) stage_slab_lds(sm + ((ci + 1) & 1) * SLAB, H, k0, kb, kc + KC, KC, NT, false);
     // a wave without a row (I >= NT: the last group of every launch) skips the MFMAs by a
-    // wave-uniform branch around the whole chunk (MHE_BIG_ROWS_SKIP); it still stages and
-    // meets the barriers
-    if (MHE_BIG_ROWS_SKIP && !act) continue;
-    if (MHE_BIG_WSKIP && kc + KC <= fI) {
+    // wave-uniform branch around the whole chunk; it still stages and meets the barriers
+    if (!act) continue;
+    if (kc + KC <= fI) {
       // the row's L_Ik of this chunk are zero (left of its f): no MFMAs; the next chunk's
       // B operands are loaded here when that chunk is the row's first nonzero one
       if (kc + KC < k0 && kc + 2 * KC > fI) {
@@ -1845,7 +1605,7 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
     }
 #pragma unroll
     for (int kk = 0; kk < KC; ++kk) {
-      if (MHE_BIG_HEAD && kc + kk >= k0) break;  // k0 odd (MHE_BIG_HEAD): no next chunk either
+      if (kc + kk >= k0) break;  // k0 odd (head block): no next chunk either
       double a0[4], a1[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) a0[r] = LJ[kk * 256 + 64 * r + lane];
@@ -1869,89 +1629,32 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
       }
     }
   }
-#else
-  for (int kc = kst; kc < k0 && !(MHE_BIG_KO & 1); kc += KC) {
-    const int ci = (kc - kst) / KC;
-    const double* LJ = sm + (DB ? (ci & 1) * SLAB : 0);
-    if (!DB && kc > kst) {
-      __syncthreads();  // the previous chunk's readers are done
-      stage_slab_lds(sm, H, k0, kb, kc, KC, NT, false);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this chunk's slab has landed
-    __syncthreads();  // ... for every wave, and the other buffer's last readers are done
-    if (DB && kc + KC < k0) stage_slab_lds(sm + ((ci + 1) & 1) * SLAB, H, k0, kb, kc + KC, KC, NT, false);
-    double bn[4];
-    const double* L0 = H + (size_t)big_tile_index(Ic, kc, NT) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bn[r] = L0[64 * r + lane];  // (kc >= kst)
-#pragma unroll
-    for (int kk = 0; kk < KC; ++kk) {
-      if (MHE_BIG_HEAD && kc + kk >= k0) break;
-      double bv[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bv[r] = bn[r];
-      if (kk + 1 < KC) {
-        const double* Ln = H + (size_t)big_tile_index(Ic, kc + kk + 1, NT) * 256;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bn[r] = Ln[64 * r + lane];
-      }
-      // the staged A operands one tile ahead
-      double a0[4], a1[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a0[r] = LJ[kk * 256 + 64 * r + lane];
-#pragma unroll
-      for (int jj = 0; jj < BIG_KB; ++jj) {
-        if (jj + 1 < BIG_KB) {
-          const int jn = min(jj + 1, kb - 1);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) a1[r] = LJ[(jn * KC + kk) * 256 + 64 * r + lane];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          acc[jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[r], bv[r], acc[jj], 0, 0, MFMA_NEG_A);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a0[r] = a1[r];
-      }
-    }
-  }
-#endif
   // the block's in-block L tiles and L_kk^-T into LDS (over the slabs)
   __syncthreads();
-  if constexpr (MHE_BIG_ROWS_LBDMA) {
-    // by LDS-DMA, every wave's share issued at once and waited for once (the load -> store
-    // loop made one L2 round trip per 8 KB: ~19 of them before the in-block chain could start)
-    const int nlb = kb * (kb - 1) / 2 * 2;  // half tiles (1 KB: one wave instruction each)
-    for (int h = wave; h < nlb; h += BIG_NW) {
-      const int slot = h >> 1;
-      int ii = 1;  // slot = ii (ii - 1) / 2 + kp, kp < ii
-      while (ii * (ii + 1) / 2 <= slot) ++ii;
-      const int kp = slot - ii * (ii - 1) / 2;
-      const double* src = H + (size_t)big_tile_index(k0 + ii, k0 + kp, NT) * 256 + 128 * (h & 1) + 2 * lane;
-      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(LB + 256 * slot + 128 * (h & 1)),
-                                       16, 0, 0);
-    }
-    const int nlt = (kb * DTS) / 2;  // 16-B chunks of the block's L_kk^-T (kb * DTS is even)
-    for (int c0 = wave * 64; c0 < nlt; c0 += BIG_NTHREADS) {
-      if (c0 + lane < nlt)
-        __builtin_amdgcn_global_load_lds((const void*)(LTg + (size_t)k0 * DTS + 2 * (c0 + lane)),
-                                         (__attribute__((address_space(3))) void*)(LTs + 2 * c0), 16, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    for (int e = threadIdx.x; e < (kb * (kb - 1) / 2) * 128; e += BIG_NTHREADS) {
-      const int slot = e >> 7;
-      int ii = 1;  // slot = ii (ii - 1) / 2 + kp, kp < ii
-      while (ii * (ii + 1) / 2 <= slot) ++ii;
-      const int kp = slot - ii * (ii - 1) / 2;
-      const double2 w = *(const double2*)(H + (size_t)big_tile_index(k0 + ii, k0 + kp, NT) * 256 + 2 * (e & 127));
-      *(double2*)(LB + 256 * slot + 2 * (e & 127)) = w;
-    }
-    for (int e = threadIdx.x; e < kb * DTS; e += BIG_NTHREADS) LTs[e] = LTg[(size_t)k0 * DTS + e];
+  // by LDS-DMA, every wave's share issued at once and waited for once (the load -> store
+  // loop made one L2 round trip per 8 KB: ~19 of them before the in-block chain could
+  // start; C3 +2.4 %, C4 0)
+  const int nlb = kb * (kb - 1) / 2 * 2;  // half tiles (1 KB: one wave instruction each)
+  for (int h = wave; h < nlb; h += BIG_NW) {
+    const int slot = h >> 1;
+    int ii = 1;  // slot = ii (ii - 1) / 2 + kp, kp < ii
+    while (ii * (ii + 1) / 2 <= slot) ++ii;
+    const int kp = slot - ii * (ii - 1) / 2;
+    const double* src = H + (size_t)big_tile_index(k0 + ii, k0 + kp, NT) * 256 + 128 * (h & 1) + 2 * lane;
+    __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(LB + 256 * slot + 128 * (h & 1)),
+                                     16, 0, 0);
   }
+  const int nlt = (kb * DTS) / 2;  // 16-B chunks of the block's L_kk^-T (kb * DTS is even)
+  for (int c0 = wave * 64; c0 < nlt; c0 += BIG_NTHREADS) {
+    if (c0 + lane < nlt)
+      __builtin_amdgcn_global_load_lds((const void*)(LTg + (size_t)k0 * DTS + 2 * (c0 + lane)),
+                                       (__attribute__((address_space(3))) void*)(LTs + 2 * c0), 16, 0, 0);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 #pragma unroll
   for (int kk = 0; kk < BIG_KB; ++kk) {
-    if (MHE_BIG_HEAD && kk >= kb) break;  // a narrow (head) block: no work past its columns
+    if (kk >= kb) break;  // a narrow (head) block: no work past its columns
     d4 cc = acc[kk];
 #pragma unroll
     for (int kp = 0; kp < kk; ++kp) {
@@ -1982,11 +1685,14 @@ __device__ __forceinline__ void big_rows_group(double* H, const double* LTg, dou
   }
 }
 
-template <int KC = MHE_BIG_ROWS_KC, bool DB = MHE_BIG_ROWS_DB != 0>
+// (DB: the slabs double-buffered, the only form; kept in the parameter list so the kernel's
+// name in profiles stays k_big_rows<2, true>)
+template <int KC = BIG_ROWS_KC, bool DB = true>
 __global__ __launch_bounds__(BIG_NTHREADS, 4) void k_big_rows(BigArgs a, int k0) {
+  static_assert(DB, "the single-buffered form is gone");
   const int G = gridDim.x;
   int b = blockIdx.y, grp = blockIdx.x;
-  if (MHE_BIG_ROWS_XCD && (gridDim.y & 7) == 0) {
+  if ((gridDim.y & 7) == 0) {
     const int L = blockIdx.x + G * blockIdx.y, x = L & 7, j = L >> 3;
     b = 8 * (j / G) + x;
     grp = j - G * (j / G);
@@ -1995,8 +1701,7 @@ __global__ __launch_bounds__(BIG_NTHREADS, 4) void k_big_rows(BigArgs a, int k0)
   const BigWs WL = big_ws_layout(a.P, a.M, a.n, a.NT, a.nz, a.nc);
   double* ws = a.ws + (size_t)b * a.ws_stride;
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  big_rows_group<KC, DB>(ws + WL.H, ws + WL.LT, ws + WL.BV, ws + WL.YV, sm, a.NT, k0, grp,
-                         MHE_BIG_ENV ? big_env_first(ws, WL, a.n) : nullptr);
+  big_rows_group<KC>(ws + WL.H, ws + WL.LT, ws + WL.BV, ws + WL.YV, sm, a.NT, k0, grp, big_env_first(ws, WL, a.n));
 }
 
 // ------------------------------------------------------------ border (f4)
@@ -2257,7 +1962,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_cov(BigArgs a, int use_env
   const double* LT = ws + WL.LT;
   const int NT = a.NT, Pp = a.Pp, dp = 16 * NT;
   double* ZQ = a.cov_scratch + (size_t)b * KP * dp;
-  const int* FI = MHE_BIG_ENV && use_env ? big_env_first(ws, WL, n) : nullptr;
+  const int* FI = use_env ? big_env_first(ws, WL, n) : nullptr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   for (int t = threadIdx.x; t < KP * dp; t += BIG_NTHREADS) {

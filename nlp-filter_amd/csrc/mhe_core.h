@@ -46,9 +46,6 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #ifndef MHE_NW
 #define MHE_NW 8
 #endif
-#ifndef MHE_SB_DIAG_BUILD
-#define MHE_SB_DIAG_BUILD 0  // A/B: small-batch instance's diagonal tiles built by waves 0 and 4 only
-#endif
 constexpr int NW = MHE_NW;
 constexpr int NTHREADS = NW * 64;
 constexpr int MAX_NT = 13;         // padded system <= 208 (register-resident path)
@@ -913,7 +910,7 @@ __device__ __forceinline__ void build_slots_n2(const GnArgs& a, const ConstLayou
 // BOUNDED (projected Newton, k_gn_bounded): rows and columns of the epsilon-active
 // unknowns (ACT) are replaced by their diagonal entries -- the reduced GN system on
 // the free unknowns, a diagonally scaled gradient step on the active ones.
-template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false, bool SB = false>
+template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false>
 __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
                                             d4 (&acc)[SLOTS], int wave, int lane, int stab) {
   const int* ACT = (const int*)(sm + SL.ACT);
@@ -1007,12 +1004,7 @@ __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& 
     if (s & 1) __builtin_amdgcn_sched_barrier(0);
   }
   double* DT = sm + SL.DT;
-  // small-batch factorization: the diagonal tiles go to the two waves without slots (CP,
-  // wave 0, and wave 4), alternately, instead of one or two to every wave -- the six
-  // slot owners build only their off-diagonal tiles (MHE_SB_DIAG_BUILD)
-  const bool sbd = SB && MHE_SB_DIAG_BUILD;
-  const int j0 = sbd ? (wave == 0 ? 0 : wave == 4 ? 1 : a.NT) : wave, js = sbd ? 2 : NW;
-  for (int J = j0; J < a.NT; J += js) {
+  for (int J = wave; J < a.NT; J += NW) {
     const int ti = tile_index(J, J, a.NT);
     const size_t off = (size_t)ti * 256 + lane;
     const int col = 16 * J + (lane & 15);
@@ -1396,26 +1388,16 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
 // instance): tests/test_gpu_parity.py::test_small_batch_instance_matches_full_occupancy_instance
 // and ::test_full_occupancy_instance_iterates_match_oracle assert it, which is what keeps
 // results independent of the GPU count a strong split runs on.
-#ifndef MHE_SB_WEIGHTED
-#define MHE_SB_WEIGHTED 0  // A/B: 7:6 weighted tile shares (factorization -10 %, build / backward slower: -3 % overall)
-#endif
-#ifndef MHE_GN_SB
-#define MHE_GN_SB 1  // 0: no small-batch factorization (A/B builds only: the round-4 small-batch instance)
-#endif
 constexpr int SB_WORKERS = 6;
-// Waves w and w + 4 share a SIMD, and the older one (1, 2, 3) wins the issue arbitration
-// of every pair, so with equal shares the younger one (5, 6, 7) finished an interval
-// ~20 % later.  The tiles are dealt by smooth weighted round robin, weights 7 : 6 for the
-// older / younger workers (0-2 = waves 1-3, 3-5 = waves 5-7): 14 and 12 tiles, and every
-// interval's active tiles split about 7 : 6 as well.
-constexpr int SB_SLOTS = MHE_SB_WEIGHTED ? 14 : (MAX_NT * (MAX_NT - 1) / 2 + SB_WORKERS - 1) / SB_WORKERS;
-__constant__ const unsigned char SB_OWNER[MAX_NT * (MAX_NT - 1) / 2] = {
-    0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2,
-    0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 0, 1, 2};
+// Tiles are dealt to the workers round robin.  (Waves w and w + 4 share a SIMD and the
+// older one wins the issue arbitration, so the younger workers finish an interval ~20 %
+// later; 7 : 6 weighted shares made the factorization 10 % faster but the build and the
+// backward solve slower: -3 % overall.)
+constexpr int SB_SLOTS = (MAX_NT * (MAX_NT - 1) / 2 + SB_WORKERS - 1) / SB_WORKERS;
 
 __device__ __forceinline__ int sb_worker(int wave) { return (wave == 0 || wave == 4) ? -1 : wave < 4 ? wave - 1 : wave - 2; }
 
-__device__ __forceinline__ int sb_owner(int u) { return MHE_SB_WEIGHTED ? SB_OWNER[u] : u % SB_WORKERS; }
+__device__ __forceinline__ int sb_owner(int u) { return u % SB_WORKERS; }
 
 // slot table of factor_forward_sb: the s-th tile (column-major over I > J) that this
 // wave's worker owns
@@ -2102,7 +2084,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       return;
     }
     if (it >= a.max_iter) break;
-    build_tiles<DYN, MEAS, SLOTS, HUBER, false, SB>(FA, FCL, FSL, sm, acc, wave, lane, stab);
+    build_tiles<DYN, MEAS, SLOTS, HUBER>(FA, FCL, FSL, sm, acc, wave, lane, stab);
     DIAG_MARK(15);
     __syncthreads();
     DIAG_MARK(2);
@@ -2610,7 +2592,7 @@ inline GnChoice gn_choice(const mhe_dims* dm, int NT, int batch, int mode, hipSt
   // a batch that gives each CU at most one trajectory runs the small-batch instance:
   // 256 VGPRs (no two-workgroups-per-CU register cap) and factor_forward_sb (C2 strong
   // scaling at 4-8 GPUs: 256 / 128 per GPU)
-  c.sb = MHE_GN_SB && mode == MODE_SOLVE && !c.bounded && !c.huber && batch <= device_cus(st) &&
+  c.sb = mode == MODE_SOLVE && !c.bounded && !c.huber && batch <= device_cus(st) &&
          smem_bytes(dm, NT, false, true) + g_opt_smem_pad <= REG_LDS_LIMIT;
   // pad: mhe_set_option, occupancy A/B only; MODE_COV: the query panel on top (dp x 16)
   c.smem = smem_bytes(dm, NT, c.bounded, c.sb, mode == MODE_COV) + g_opt_smem_pad;
@@ -2664,34 +2646,29 @@ int launch_build_cc(const mhe_dims* dm, int NT, const double* D, const double* c
 // The factorization of the large-system path: left-looking block-column updates (default;
 // 38 % less HBM traffic than the right-looking trailing update, C3 +5 %, C4 +7.5 %, C5 +8 %);
 // the right-looking form (bitwise-identical iterates, tests/test_gpu_big.py) only when a
-// caller selected it with mhe_set_option(MHE_OPT_BIG_RIGHT_LOOKING, 1).  MHE_BIG_SPLIT: the
-// left-looking form as launches per block column (k_big_chol SPLIT = 1, then k_big_rows over
-// the rows below, one workgroup per 8 rows) and one for the solve (SPLIT = 2) -- for wide
-// systems by default: C4 +8.9 %, C5 +8.2 %, but C3 -5 % (profiles/r05_ab_big_split.txt).
+// caller selected it with mhe_set_option(MHE_OPT_BIG_RIGHT_LOOKING, 1).  The left-looking
+// form is always split: launches per block column (k_big_chol SPLIT = 1, then k_big_rows over
+// the rows below, one workgroup per 8 rows) and one for the solve (SPLIT = 2) -- C4 +8.9 %,
+// C5 +8.2 % over one launch (profiles/r05_ab_big_split.txt), and since round 6 C3 too.
 struct BigCholPlan {
-  void (*mono)(BigArgs, int);
-  void (*diag)(BigArgs, int);
-  void (*bwd)(BigArgs, int);
+  void (*mono)(BigArgs, int);  // the right-looking factorization and solve, one launch (!split)
+  void (*diag)(BigArgs, int);  // split: a block column's diagonal stage
+  void (*bwd)(BigArgs, int);   // split: the backward solve
   int smem, smem_rows, smem_diag;
-  bool split;
+  bool split;  // the left-looking form
 };
 // prec: the instances with the pivots' second Newton step (BIG_STAGE_COV)
 inline int big_chol_plan(const BigArgs& A, BigCholPlan& p, bool prec = false) {
   const bool wide = A.NT >= BIG_WIDE_NT;
   p.smem = big_chol_lds(wide ? 8 : 4) * (int)sizeof(double);
   p.smem_rows = big_rows_lds() * (int)sizeof(double);
-  const bool ll = g_opt_big_right_looking == 0;
-  p.split = ll && (MHE_BIG_SPLIT == 1 || (MHE_BIG_SPLIT == 2 && wide));
-  p.mono = wide ? (ll ? k_big_chol<8, true> : k_big_chol<8>) : (ll ? k_big_chol<4, true> : k_big_chol<4>);
-  if (prec)
-    p.mono = wide ? (ll ? k_big_chol<8, true, 0, true> : k_big_chol<8, false, 0, true>)
-                  : (ll ? k_big_chol<4, true, 0, true> : k_big_chol<4, false, 0, true>);
-  // the split diagonal stage stages a kb x 4 slab at any width (MHE_BIG_DIAG_REG): the
-  // 4-wide instance's LDS, two workgroups per CU
-  const bool d4w = MHE_BIG_DIAG_REG != 0;
-  p.diag = wide && !d4w ? k_big_chol<8, true, 1> : k_big_chol<4, true, 1>;
-  if (prec) p.diag = wide && !d4w ? k_big_chol<8, true, 1, true> : k_big_chol<4, true, 1, true>;
-  p.smem_diag = big_chol_lds(wide && !d4w ? 8 : 4) * (int)sizeof(double);
+  p.split = g_opt_big_right_looking == 0;
+  p.mono = wide ? k_big_chol<8> : k_big_chol<4>;
+  if (prec) p.mono = wide ? k_big_chol<8, false, 0, true> : k_big_chol<4, false, 0, true>;
+  // the split diagonal stage keeps its rows' update in registers and stages small slabs at
+  // any width: the 4-wide instance's LDS, two workgroups per CU
+  p.diag = prec ? k_big_chol<4, true, 1, true> : k_big_chol<4, true, 1>;
+  p.smem_diag = big_chol_lds(4) * (int)sizeof(double);
   p.bwd = wide ? k_big_chol<8, true, 2> : k_big_chol<4, true, 2>;
   for (auto f : {p.mono, p.bwd})
     if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, p.smem) != hipSuccess)
@@ -2753,13 +2730,13 @@ inline BigAux* big_aux(hipStream_t st) {
 // The factorization + solve.  Split: the two halves of the batch go through the stages on
 // two streams, so one half's latency-bound diagonal stages and solve overlap the other
 // half's row launches (what the one-launch kernel gets from trajectories at different
-// phases) -- MHE_BIG_TWO_STREAMS.
+// phases; C5 +6.2 %, C3 +1.5 %, C4 0).
 inline void launch_big_factor(const BigCholPlan& p, const BigArgs& A, int batch, hipStream_t st) {
   if (!p.split) {
     hipLaunchKernelGGL(p.mono, dim3(batch), dim3(BIG_NTHREADS), p.smem, st, A, 0);
     return;
   }
-  BigAux* aux = MHE_BIG_TWO_STREAMS && batch >= 16 ? big_aux(st) : nullptr;
+  BigAux* aux = batch >= 16 ? big_aux(st) : nullptr;
   if (!aux) {
     launch_big_split(p, A, 0, batch, st);
     return;
@@ -2792,12 +2769,12 @@ inline BigAsmShape big_asm_shape(const BigArgs& A) {
   return s;
 }
 
-// k_big_resid with its dynamic LDS (X staged when MHE_BIG_RESID_LDS: P n doubles; C5 64 KB)
+// k_big_resid with its dynamic LDS (X staged: P n doubles; C5 64 KB)
 template <class DYN, class MEAS>
 inline int launch_big_resid(const BigArgs& A, int batch, int final_pass, hipStream_t st) {
-  const int smem = MHE_BIG_RESID_LDS ? A.P * A.n * (int)sizeof(double) : 0;
-  if (smem > 0 && hipFuncSetAttribute((const void*)k_big_resid<DYN, MEAS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      smem) != hipSuccess)
+  const int smem = A.P * A.n * (int)sizeof(double);
+  if (hipFuncSetAttribute((const void*)k_big_resid<DYN, MEAS>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
+      hipSuccess)
     return MHE_ERR_HIP;
   hipLaunchKernelGGL((k_big_resid<DYN, MEAS>), dim3(batch), dim3(BIG_NTHREADS), smem, st, A, final_pass);
   return MHE_OK;

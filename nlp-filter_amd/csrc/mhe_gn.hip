@@ -350,11 +350,10 @@ __global__ void k_big_parity_init(BigArgs a, int batch) {
     const bool ok = *(const unsigned long long*)a.cbuf == a.tag;
     a.state[b] = ok ? BIG_RUNNING : MHE_STATUS_BAD_CONSTANTS;
     if (!ok && a.cost) a.cost[b] = NAN;
-    if (MHE_BIG_ENV) {  // the envelope flags k_big_import_hg sets from the caller's system
-      const BigWs WL = big_ws_layout(a.P, a.M, a.n, a.NT, a.nz, a.nc);
-      int* EM = big_env_mask(a.ws + (size_t)b * a.ws_stride, WL);
-      for (int e = 0; e < a.n * a.n; ++e) EM[e] = 0;
-    }
+    // the envelope flags k_big_import_hg sets from the caller's system
+    const BigWs WL = big_ws_layout(a.P, a.M, a.n, a.NT, a.nz, a.nc);
+    int* EM = big_env_mask(a.ws + (size_t)b * a.ws_stride, WL);
+    for (int e = 0; e < a.n * a.n; ++e) EM[e] = 0;
   }
 }
 
@@ -430,7 +429,7 @@ __global__ void k_big_import_hg(BigArgs a, int batch, int ld, const double* Hin,
   const double v = Hin[((size_t)b * ld + hi) * ld + lo];
   ws[WL.H + (size_t)blockIdx.x * 256 + threadIdx.x] = v;
   if (I == J && tr == 0) ws[WL.BV + 16 * I + tc] = -gin[(size_t)b * ld + (C % a.Pp) * a.n + C / a.Pp];
-  if (MHE_BIG_ENV && __syncthreads_or(v != 0.0) && threadIdx.x == 0) {  // component pair flags (envelope)
+  if (__syncthreads_or(v != 0.0) && threadIdx.x == 0) {  // component pair flags (envelope)
     int* EM = big_env_mask(ws, WL);
     const int ca = I / a.NTc, cb = J / a.NTc;
     EM[ca * a.n + cb] = 1;
@@ -754,12 +753,11 @@ int32_t mhe_solve_kernel_name(const mhe_dims* dims, int32_t batch, void* stream,
   if (!buf || len <= 0) return MHE_ERR_NULL;
   if (is_big(dims)) {
     BigArgs A = make_big_args(dims, nullptr, NT, nullptr);
-    const bool wide = A.NT >= BIG_WIDE_NT, split = g_opt_big_right_looking == 0 && (MHE_BIG_SPLIT == 1 ||
-                                                                                      (MHE_BIG_SPLIT == 2 && wide));
-    snprintf(buf, len, "large-system path (dyn %d, meas %d, NT %d): k_big_resid, k_big_assemble, %s%s, k_big_%s",
+    const bool wide = A.NT >= BIG_WIDE_NT, split = g_opt_big_right_looking == 0;
+    snprintf(buf, len, "large-system path (dyn %d, meas %d, NT %d): k_big_resid, k_big_assemble, %s, k_big_%s",
              dims->dyn_model, dims->meas_model, NT,
-             split ? "k_big_chol<8|4, LL, split stages> + k_big_rows" : (wide ? "k_big_chol<8" : "k_big_chol<4"),
-             split ? "" : (g_opt_big_right_looking ? ">" : ", LL>"), dims->n_bounds > 0 ? "linesearch" : "update");
+             split ? "k_big_chol<8|4, LL, split stages> + k_big_rows" : (wide ? "k_big_chol<8>" : "k_big_chol<4>"),
+             dims->n_bounds > 0 ? "linesearch" : "update");
     return MHE_OK;
   }
   const GnChoice c = gn_choice(dims, NT, batch, MODE_SOLVE, (hipStream_t)stream);
@@ -775,7 +773,7 @@ int32_t mhe_big_envelope(const mhe_dims* dims, const void* workspace, size_t wor
   int NT = 0;
   const int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
-  if (!is_big(dims) || !MHE_BIG_ENV) return MHE_ERR_UNSUPPORTED;
+  if (!is_big(dims)) return MHE_ERR_UNSUPPORTED;
   if (!workspace || !first_col) return MHE_ERR_NULL;
   if (n_out < NT || traj < 0) return MHE_ERR_DIMS;
   const BigArgs A = make_big_args(dims, nullptr, NT, const_cast<void*>(workspace));

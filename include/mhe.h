@@ -111,7 +111,7 @@ extern "C" {
  * the size queries) unless it equals this build's sizeof -- a binding that
  * declares an older or truncated struct is refused before any later field is
  * read.  (mhe/_lib.py sets it in the ctypes constructors.) */
-#define MHE_ABI_VERSION 8
+#define MHE_ABI_VERSION 9
 
 typedef struct mhe_dims {
   int32_t struct_size;  /* = sizeof(mhe_dims)                                */
@@ -288,6 +288,24 @@ int mhe_gn_solve_ext(const mhe_dims* dims, const void* const_buf, int32_t batch,
  *                       constants buffer for all windows.  Nonlinear measurement
  *                       models only (a linear h has Rw folded into the constant
  *                       part of J^T W J): MHE_ERR_UNSUPPORTED otherwise.
+ *
+ * Robust measurement rows (ABI v9).  meas_delta (B|1, M) puts the reference's
+ * pseudo_huber_loss (cost_functions.py:25-31, Q = R_i) on the scalar measurement rows
+ * (p = 1: pseudorange, vehicle_pseudorange, range_3d and every MHE_MEAS_MIXED row code).
+ * Row i with weight R_i (Rw or the constants'), residual e_i and scale delta_i (in the
+ * row's own units) costs
+ *   2 R_i delta_i^2 (sqrt(1 + e_i^2 / delta_i^2) - 1)
+ *     = 2 R_i e_i^2 / (1 + sqrt(1 + e_i^2 / delta_i^2))      (the form evaluated)
+ * and the solve is IRLS, as for MHE_COST_HUBER: each GN step uses the row weight
+ *   lambda_i = R_i / sqrt(1 + e_i^2 / delta_i^2)
+ * (GE_i = H_i^T lambda_i e_i, G_i = H_i^T lambda_i H_i; the bounded solve's Armijo noise
+ * term uses |lambda_i e_i|).  delta_i = +inf selects the plain quadratic row by a branch:
+ * that row is bitwise the row of a call with meas_delta = NULL.  R_i = 0 masks the row
+ * whatever delta_i is.  delta_i must be > 0 (NaN excluded): the host wrappers check it,
+ * these entry points do NOT.  mhe_solve, mhe_state_cov (the covariance then uses the IRLS
+ * weights at X) and mhe_assemble_at honour it; cost_out is the robust objective.  A linear
+ * measurement model (MHE_MEAS_FULL_STATE: R is folded into the constants) and p > 1 return
+ * MHE_ERR_UNSUPPORTED.  NULL: every call runs exactly the kernels it ran before v9.
  */
 typedef struct mhe_solve_args {
   int32_t struct_size;     /* = sizeof(mhe_solve_args) */
@@ -314,6 +332,9 @@ typedef struct mhe_solve_args {
   double* lambda_out;      /* optional (B, n_eq): multipliers of the constraint rows from the
                               last bordered step, L = J + lambda^T (C v - r) (their signs
                               drive the host's active set), or NULL */
+  const double* meas_delta; /* optional (B|1, M): pseudo-Huber scale per measurement row (ABI v9,
+                               see "Robust measurement rows" below), or NULL = quadratic rows */
+  int64_t md_bstride;       /* batch stride of meas_delta; 0 = shared by the batch */
 } mhe_solve_args;
 
 int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* args, void* stream);
@@ -430,12 +451,21 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
                         const double* x0, double* H, double* g, double* cost, int32_t* status,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* mhe_assemble_kkt_ws taking the struct (ABI v9): the kernel-level view of the per-solve
+ * inputs the positional mhe_assemble* calls cannot carry.  at->X0 is the point (B, P, n);
+ * Z0 (n_extra > 0), U, Y, PAR, Rw, meas_delta, x0 with their strides, batch and (large-
+ * system path) workspace / workspace_bytes are read from the struct; its outputs and
+ * max_iter / tol are not.  H, g, cost, status as mhe_assemble_kkt_ws: with meas_delta the
+ * IRLS system at X (the weights lambda_i above) and the robust cost. */
+int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at,
+                    double* H, double* g, double* cost, int32_t* status, void* stream);
+
 /* Posterior covariance of the state estimate at query times (ABI v8).
  *
  * The objective is r^T W r, so H = J^T W J at the point X is the information matrix of
  * the whole trajectory, and with S_t = phi(t)^T (x) I_n (the Lagrange row extractSolution
  * uses)  Cov[x(t)] = S_t H^-1 S_t^T.  The call assembles H at X exactly as a solve does
- * (Huber IRLS weights, the per-solve Rw), runs the solve's own Cholesky factorization
+ * (Huber IRLS weights, the per-solve Rw and meas_delta), runs the solve's own Cholesky factorization
  * H = U^T U (on the large-system path with the pivots refined once more) and sweeps the query columns through the factor: Z = U^-T S_t^T, Cov = Z^T Z
  * (a multi-column forward substitution; no back substitution, no inverse).
  *
@@ -447,7 +477,7 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
  * projected quantity), as does n > 16 on the register-resident path, and a problem
  * whose query panel (dp x 16 doubles of LDS on top of the solve's) does not fit.
  *
- *   at          batch; X0 = the point (B, P, n); U, Y, PAR, x0, Rw and their strides, and
+ *   at          batch; X0 = the point (B, P, n); U, Y, PAR, x0, Rw, meas_delta and their strides, and
  *               on the large-system path workspace / workspace_bytes, as for mhe_solve.
  *               The outputs and max_iter / tol of the struct are not read.
  *   PhiQ        (n_query, P) DEVICE: Lagrange basis rows at the query times

@@ -165,11 +165,30 @@ struct BigArgs {
   int nq;
   double* cov;
   double* cov_scratch;
+  const double* md;  // pseudo-Huber scale per measurement row (B|1, M) or NULL (mhe_solve_args.meas_delta)
+  long long mdstride;
 };
 
 // measurement weights of trajectory b: the per-solve array when given, else the constants'
 __device__ __forceinline__ const double* big_rw(const BigArgs& a, const double* Rc, int b) {
   return a.Rw ? a.Rw + (long long)b * a.rwstride : Rc;
+}
+
+// robust measurement rows (scalar rows): trajectory b's scales, or NULL = quadratic rows
+__device__ __forceinline__ const double* big_md(const BigArgs& a, int b) {
+  return a.md ? a.md + (long long)b * a.mdstride : nullptr;
+}
+// Row i's pseudo-Huber reweighting (meas_row, mhe_core.h): with s = sqrt(1 + e^2 / delta_i^2)
+// R becomes the IRLS weight R / s and the row's cost 2 R e^2 / (1 + s); false (R untouched:
+// the quadratic row's own arithmetic) without scales or for delta_i = +inf.
+__device__ __forceinline__ bool big_row_huber(const double* md, int i, double ev, double& R, double& rcost) {
+  if (!md) return false;
+  const double dl = md[i];
+  if (!(dl < INFINITY)) return false;
+  const double sr = sqrt(1.0 + ev * ev / (dl * dl));
+  rcost = 2.0 * R * ev * ev / (1.0 + sr);
+  R = R / sr;
+  return true;
 }
 
 __device__ __forceinline__ int big_tile_index(int I, int J, int NT) { return J * NT - J * (J - 1) / 2 + (I - J); }
@@ -302,7 +321,9 @@ __device__ void big_nodes_sparse(const BigArgs& a, const BigConst& CL, const Big
   }
 }
 
-template <class DYN, class MEAS>
+// MHUBER: the instances a call with meas_delta runs (robust scalar rows, big_row_huber); the
+// others never read a.md
+template <class DYN, class MEAS, bool MHUBER = false>
 __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final_pass) {
   constexpr int n = DYN::n, m = DYN::m, p = MEAS::p, q = MEAS::q;
   const int b = blockIdx.x;
@@ -324,6 +345,8 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
   const double* Qw = (const double*)(a.cbuf + CL.Qw);
   const double* Pw = (const double*)(a.cbuf + CL.Pw);
   const double* Rw = big_rw(a, (const double*)(a.cbuf + CL.Rw), b);
+  const double* md = nullptr;
+  if constexpr (MHUBER) md = big_md(a, b);
   const double* PhiE = (const double*)(a.cbuf + CL.PhiE);
   const double* PhiET = (const double*)(a.cbuf + CL.PhiET);
   const int* erow = (const int*)(a.cbuf + CL.erow);
@@ -338,6 +361,9 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
   const double* X = xl_dyn;
   __shared__ double red[2 * BIG_NW];
   double cost = 0.0, noise = 0.0;  // noise: the cost's rounding level (bounded problems' line search)
+  // the robust rows' cost, summed apart: a quadratic row keeps its own statement (and its
+  // contraction into one fma), so delta = +inf is bitwise the call without meas_delta
+  double rc = 0.0;
   // interpolated states at the epochs: x_e = sum_j Phi_E[e][j] X_j
   for (int e = threadIdx.x; e < E; e += BIG_NTHREADS) {
     double xe[n];
@@ -436,7 +462,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
       }
       for (int i = erow[e]; i < erow[e + 1]; ++i) {
         const double* PR = a.PAR + (long long)b * a.pstride + (long long)i * q;
-        const double R = Rw[i];
+        double R = Rw[i];
         if (R == 0.0) continue;  // R = 0 masks the row (empty satellite slot, autonomous-car.py:260-263)
         // per-slot gradient: a component in two slots gets their sum (two terms: the same
         // value as the dense accumulation), zero gradients dropped -- the dense form's
@@ -457,8 +483,12 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
 #pragma unroll
         for (int k1 = 0; k1 < 7; ++k1)
           if (gs[k1] == 0.0) id[k1] = -1;
-        const double yv = a.Y[(long long)b * a.M + i], ev = yv - h, Re = R * ev;
-        cost += ev * Re;
+        const double yv = a.Y[(long long)b * a.M + i], ev = yv - h;
+        double rcost;
+        const bool robust = big_row_huber(md, i, ev, R, rcost);  // R <- the IRLS weight
+        const double Re = R * ev;
+        if (robust) rc += rcost;
+        else cost += ev * Re;
         noise += fabs(Re) * (fabs(yv) + fabs(h));
 #pragma unroll
         for (int u = 0; u < 7; ++u) {
@@ -500,11 +530,19 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
       const double* yi = a.Y + ((long long)b * a.M + i) * p;
       double ev[p], Re[p];
       for (int r = 0; r < p; ++r) ev[r] = yi[r] - h[r];
+      double lam[p], rcost = 0.0;  // robust scalar rows: the IRLS weight in R's place
+      bool robust = false;
+      if constexpr (p == 1) {
+        lam[0] = R[0];
+        robust = big_row_huber(md, i, ev[0], lam[0], rcost);
+        if (robust) R = lam;
+      }
       for (int r = 0; r < p; ++r) {
         double s = 0.0;
         for (int c = 0; c < p; ++c) s += R[r * p + c] * ev[c];
         Re[r] = s;
-        cost += ev[r] * s;
+        if (robust) rc += rcost;
+        else cost += ev[r] * s;
         noise += fabs(s) * (fabs(yi[r]) + fabs(h[r]));
       }
       for (int c = 0; c < n; ++c) {
@@ -555,6 +593,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if constexpr (MHUBER) cost += rc;
   cost = wave_sum(cost);
   noise = wave_sum(noise);
   if (lane == 0) {
@@ -2101,7 +2140,7 @@ struct MeasArgLen<MEAS, n, true> {
   static constexpr int v = MEAS::NA;
 };
 
-template <class DYN, class MEAS>
+template <class DYN, class MEAS, bool MHUBER = false>
 __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red, double& nz_out) {
   constexpr int n = DYN::n, m = DYN::m, p = MEAS::p, q = MEAS::q, NAX = MeasArgLen<MEAS, n>::v;
   const BigConst CL = big_const_layout(a.P, a.M, n, p, a.nc);
@@ -2110,11 +2149,13 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
   const double* Qw = (const double*)(a.cbuf + CL.Qw);
   const double* Pw = (const double*)(a.cbuf + CL.Pw);
   const double* Rw = big_rw(a, (const double*)(a.cbuf + CL.Rw), b);
+  const double* md = nullptr;
+  if constexpr (MHUBER) md = big_md(a, b);
   const double* PhiET = (const double*)(a.cbuf + CL.PhiET);
   const int* erow = (const int*)(a.cbuf + CL.erow);
   const int E = a.M > 0 ? *(const int*)(a.cbuf + CL.ne) : 0;
   const int Mr = a.M > 0 ? a.M : 1;
-  double cost = 0.0, noise = 0.0;
+  double cost = 0.0, noise = 0.0, rc = 0.0;  // rc: the robust rows' cost (as k_big_resid)
   for (int k = threadIdx.x; k < a.P; k += BIG_NTHREADS) {
     double dx[n], xk[n], uk[m > 0 ? m : 1], f[n];
     for (int c = 0; c < n; ++c) dx[c] = 0.0;
@@ -2162,12 +2203,15 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
     for (int i = erow[e]; i < erow[e + 1]; ++i) {
       if constexpr (MEAS::MIXED) {
         const double* PR = a.PAR + (long long)b * a.pstride + (long long)i * q;
-        const double R = Rw[i];
+        double R = Rw[i];
         if (R == 0.0) continue;
         double h, Gr[NAX];
         MEAS::eval(xe, PR, 0, h, Gr);
         const double yv = a.Y[(long long)b * a.M + i], ev = yv - h;
-        cost += ev * (R * ev);
+        double rcost;
+        const bool robust = big_row_huber(md, i, ev, R, rcost);  // as k_big_resid
+        if (robust) rc += rcost;
+        else cost += ev * (R * ev);
         noise += fabs(R * ev) * (fabs(yv) + fabs(h));
       } else {
         double par[q > 0 ? q : 1];
@@ -2182,10 +2226,18 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
         const double* yi = a.Y + ((long long)b * a.M + i) * p;
         double ev[p];
         for (int r = 0; r < p; ++r) ev[r] = yi[r] - h[r];
+        double lam[p], rcost = 0.0;  // robust scalar rows, as k_big_resid
+        bool robust = false;
+        if constexpr (p == 1) {
+          lam[0] = R[0];
+          robust = big_row_huber(md, i, ev[0], lam[0], rcost);
+          if (robust) R = lam;
+        }
         for (int r = 0; r < p; ++r) {
           double s = 0.0;
           for (int c = 0; c < p; ++c) s += R[r * p + c] * ev[c];
-          cost += ev[r] * s;
+          if (robust) rc += rcost;
+          else cost += ev[r] * s;
           noise += fabs(s) * (fabs(yi[r]) + fabs(h[r]));
         }
       }
@@ -2199,6 +2251,7 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if constexpr (MHUBER) cost += rc;
   cost = wave_sum(cost);
   noise = wave_sum(noise);
   __syncthreads();
@@ -2220,7 +2273,7 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
 // Bounded problems: replaces k_big_update.  Stationarity measure s = P(X + d) - X,
 // Armijo search along P(X + a d) (trial iterates in LDS, cost by big_cost), X <-
 // accepted trial, convergence max|s| <= tol (1 + max|X|).  Constants as k_gn_bounded.
-template <class DYN, class MEAS>
+template <class DYN, class MEAS, bool MHUBER = false>
 __global__ __launch_bounds__(BIG_NTHREADS) void k_big_linesearch(BigArgs a) {
   constexpr int n = DYN::n;
   const int b = blockIdx.x;
@@ -2264,7 +2317,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_linesearch(BigArgs a) {
     }
     __syncthreads();
     double nzt;
-    const double ct = big_cost<DYN, MEAS>(a, xt, b, red, nzt);
+    const double ct = big_cost<DYN, MEAS, MHUBER>(a, xt, b, red, nzt);
     pred = wave_sum(pred);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = pred;
     __syncthreads();

@@ -186,6 +186,8 @@ struct GnArgs {
   const double* PhiQ;       // MODE_COV: (nq, P) Lagrange rows at the query times
   int nq;
   double* cov;              // MODE_COV: (B, nq, n, n)
+  const double* md;         // pseudo-Huber scale per measurement row (B|1, M) or NULL (mhe_solve_args.meas_delta):
+  long long mdstride;       //   read by the MHUBER instances only
 };
 
 #ifdef MHE_DIAG
@@ -524,9 +526,15 @@ __device__ __forceinline__ double node_phase(const GnArgs& a, const ConstLayout&
 // NOISE (projected Newton's Armijo test only): also accumulate into *nzp the rounding
 // level of this row's cost, COST_NOISE eps |R e| (|y| + |h|) -- e = y - h carries
 // eps (|y| + |h|) of rounding in any evaluation order (oracle/gn.py cost_noise).
+//
+// MHUBER (mhe_solve_args.meas_delta, scalar rows): pseudo_huber_loss with Q = R_i on the
+// row, by IRLS as the dynamics HUBER -- with s = sqrt(1 + e^2 / delta_i^2) the weight
+// lambda_i = R_i / s replaces R_i in GE_i, G_i and the noise term, and the row costs
+// 2 R_i e^2 / (1 + s) (= 2 R_i delta^2 (s - 1) without the cancellation at |e| << delta).
+// delta_i = +inf takes the quadratic row's own code (a branch: no inf * 0).
 constexpr double COST_NOISE = 4.0;
 
-template <class DYN, class MEAS, bool NOISE = false>
+template <class DYN, class MEAS, bool NOISE = false, bool MHUBER = false>
 __device__ __forceinline__ double meas_row(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
                                            int b, int i, const double (&xi)[DYN::n], double* nzp = nullptr) {
   constexpr int n = DYN::n, p = MEAS::p, q = MEAS::q;
@@ -553,6 +561,20 @@ __device__ __forceinline__ double meas_row(const GnArgs& a, const ConstLayout& C
 #pragma unroll
       for (int r = 0; r < p; ++r) e[r] = 0.0;
     }
+    [[maybe_unused]] double lam[p], rcost = 0.0;  // MHUBER: the row's IRLS weight and robust cost
+    [[maybe_unused]] bool robust = false;
+    if constexpr (MHUBER) {
+      static_assert(p == 1 && !MEAS::LINEAR, "robust measurement rows: scalar rows of a nonlinear model");
+      lam[0] = R[0];
+      const double dl = a.md[(long long)b * a.mdstride + i];
+      if (!masked && dl < INFINITY) {
+        const double sr = sqrt(1.0 + e[0] * e[0] / (dl * dl));
+        lam[0] = R[0] / sr;
+        rcost = 2.0 * R[0] * e[0] * e[0] / (1.0 + sr);
+        robust = true;
+      }
+      R = lam;
+    }
 #pragma unroll
     for (int r = 0; r < p; ++r) {
       double s = 0.0;
@@ -560,6 +582,9 @@ __device__ __forceinline__ double meas_row(const GnArgs& a, const ConstLayout& C
       for (int c = 0; c < p; ++c) s += R[r * p + c] * e[c];
       Re[r] = s;
       cost += e[r] * s;
+    }
+    if constexpr (MHUBER) {
+      if (robust) cost = rcost;
     }
     if constexpr (NOISE) {
       if (!masked) {
@@ -603,7 +628,7 @@ __device__ __forceinline__ double meas_row(const GnArgs& a, const ConstLayout& C
   return cost;
 }
 
-template <class DYN, class MEAS, bool NOISE = false>
+template <class DYN, class MEAS, bool NOISE = false, bool MHUBER = false>
 __device__ __forceinline__ double meas_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm, int b,
                                              double* nzp = nullptr) {
   constexpr int n = DYN::n;
@@ -618,7 +643,7 @@ __device__ __forceinline__ double meas_phase(const GnArgs& a, const ConstLayout&
     double xi[n];
     dot_rows_part<n>(PhiT, a.M, ii, a.P, part, Xs, xi);
     if (part || i >= a.M) continue;
-    cost += meas_row<DYN, MEAS, NOISE>(a, CL, SL, sm, b, i, xi, nzp);
+    cost += meas_row<DYN, MEAS, NOISE, MHUBER>(a, CL, SL, sm, b, i, xi, nzp);
   }
   return cost;
 }
@@ -643,13 +668,13 @@ __device__ __forceinline__ double upper_half(double v) {
 // node_phase + meas_phase.  When both row counts fit one pass (P, M <= 128 with
 // 4 lanes per row: C1, C2) each lane runs its D-row and Phi-row dots together,
 // 16 L2 loads in flight instead of 8, halving the dependent round trips.
-template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false>
+template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false>
 __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL,
                                                   double* sm, int b, DIAG_FDECL, double* nzp = nullptr) {
   constexpr int n = DYN::n;
   constexpr int ROWS = NTHREADS / TPR;
   if (a.P > ROWS || a.M > ROWS)
-    return node_phase<DYN, HUBER>(a, CL, SL, sm, b) + meas_phase<DYN, MEAS, NOISE>(a, CL, SL, sm, b, nzp);
+    return node_phase<DYN, HUBER>(a, CL, SL, sm, b) + meas_phase<DYN, MEAS, NOISE, MHUBER>(a, CL, SL, sm, b, nzp);
   const __amdgpu_buffer_rsrc_t rs = cbuf_rsrc(a.cbuf, CL.total);
   const double* Xs = sm + SL.Xs;
   // the TPR = 4 parts of a row are the four 16-lane rows of a wave (row = 16 wave +
@@ -710,16 +735,16 @@ __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLa
   double cost = 0.0;
   if (part == 0) {
     if (r < a.P) cost += node_row<DYN, HUBER>(a, CL, SL, sm, b, r, dx);
-    if (r < a.M) cost += meas_row<DYN, MEAS, NOISE>(a, CL, SL, sm, b, r, xi, nzp);
+    if (r < a.M) cost += meas_row<DYN, MEAS, NOISE, MHUBER>(a, CL, SL, sm, b, r, xi, nzp);
   }
   return cost;
 }
 
-template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false>
+template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false>
 __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL,
                                                   double* sm, int b, double* nzp = nullptr) {
   DIAG_DECL
-  return node_meas_phase<DYN, MEAS, HUBER, NOISE>(a, CL, SL, sm, b, DIAG_FARGS, nzp);
+  return node_meas_phase<DYN, MEAS, HUBER, NOISE, MHUBER>(a, CL, SL, sm, b, DIAG_FARGS, nzp);
 }
 
 // Gradient g = J^T W r (nlp/nlp.py:242-286 objective); writes BV = -g (padding 0).
@@ -1973,7 +1998,9 @@ __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL,
 // per CU, 128 VGPRs; 2 = the small-batch instance (batch <= CUs: one workgroup per CU
 // anyway), which may use 256 VGPRs
 // SB: the small-batch factorization (factor_forward_sb, MODE_SOLVE with MINW = 2 only)
-template <class DYN, class MEAS, int SLOTS, int mode, bool HUBER = false, int MINW = MHE_GN_MINW, bool SB = false>
+// MHUBER: robust measurement rows (meas_row; a.md is read)
+template <class DYN, class MEAS, int SLOTS, int mode, bool HUBER = false, int MINW = MHE_GN_MINW, bool SB = false,
+          bool MHUBER = false>
 __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   constexpr int n = DYN::n;
   static_assert(!SB || (mode == MODE_SOLVE && MINW <= 2 && NW == 8), "small-batch factorization: one workgroup per CU");
@@ -2028,7 +2055,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   DIAG_DECL
   for (;;) {
     DIAG_MARK(7);
-    double c1 = node_meas_phase<DYN, MEAS, HUBER>(FA, FCL, FSL, sm, opaque_s(b), DIAG_FARGS);
+    double c1 = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER>(FA, FCL, FSL, sm, opaque_s(b), DIAG_FARGS);
     DIAG_MARK(6);
     __syncthreads();
     DIAG_MARK(0);
@@ -2123,7 +2150,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     if (dmax <= a.tol * (1.0 + xmax)) {
       status = MHE_STATUS_CONVERGED;
       // final cost at the converged iterate
-      double cf = node_meas_phase<DYN, MEAS, HUBER>(FA, FCL, FSL, sm, opaque_s(b));
+      double cf = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER>(FA, FCL, FSL, sm, opaque_s(b));
       __syncthreads();
       cf += grad_phase<DYN>(FA, FCL, FSL, sm, opaque_s(b));
       double z = 0.0;
@@ -2198,7 +2225,7 @@ __device__ __forceinline__ double prior_cost(const GnArgs& a, const double* Pw, 
 
 #define FSLB smem_layout(opaque_s(a.P), opaque_s(a.M), n, opaque_s(a.NT), !MEAS::LINEAR, true)
 
-template <class DYN, class MEAS, int SLOTS, bool HUBER = false>
+template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool MHUBER = false>
 __global__ __launch_bounds__(NTHREADS, MHE_GN_MINW) void k_gn_bounded(GnArgs a) {
   constexpr int n = DYN::n;
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -2232,7 +2259,7 @@ __global__ __launch_bounds__(NTHREADS, MHE_GN_MINW) void k_gn_bounded(GnArgs a) 
   for (int t = threadIdx.x; t < 16 * a.NT; t += NTHREADS) ACT[t] = 0;
   __syncthreads();
   double nz0 = 0.0;  // rounding level of the cost at the iterate (Armijo slack, oracle cost_noise)
-  double cost = node_meas_phase<DYN, MEAS, HUBER, true>(FA, FCL, FSLB, sm, opaque_s(b), &nz0);
+  double cost = node_meas_phase<DYN, MEAS, HUBER, true, MHUBER>(FA, FCL, FSLB, sm, opaque_s(b), &nz0);
   __syncthreads();
   cost += grad_phase<DYN>(FA, FCL, FSLB, sm, opaque_s(b));
   block_reduce2(RED, cost, nz0, false);
@@ -2297,7 +2324,7 @@ __global__ __launch_bounds__(NTHREADS, MHE_GN_MINW) void k_gn_bounded(GnArgs a) 
       }
       __syncthreads();
       nzt = 0.0;
-      ct = node_meas_phase<DYN, MEAS, HUBER, true>(FA, FCL, FSLB, sm, opaque_s(b), &nzt);
+      ct = node_meas_phase<DYN, MEAS, HUBER, true, MHUBER>(FA, FCL, FSLB, sm, opaque_s(b), &nzt);
       if (threadIdx.x == 0 && a.has_prior)
         ct += prior_cost<n>(a, (const double*)(a.cbuf + FCL.Pw), Xs, b);
       block_reduce2(RED, ct, pred, false);
@@ -2582,17 +2609,19 @@ inline int device_cus(hipStream_t st) {
 // for the records that name it): a function of the dims, the mode and the batch against
 // the launch stream's CU count only.
 struct GnChoice {
-  bool bounded, huber, sb;
+  bool bounded, huber, sb, mhuber;
   int smem;
 };
-inline GnChoice gn_choice(const mhe_dims* dm, int NT, int batch, int mode, hipStream_t st) {
+// mhuber: the call carries meas_delta (robust measurement rows: the MHUBER instances)
+inline GnChoice gn_choice(const mhe_dims* dm, int NT, int batch, int mode, hipStream_t st, bool mhuber = false) {
   GnChoice c;
   c.bounded = mode == MODE_SOLVE && dm->n_bounds > 0;
   c.huber = dm->dyn_cost == MHE_COST_HUBER;
+  c.mhuber = mhuber;
   // a batch that gives each CU at most one trajectory runs the small-batch instance:
   // 256 VGPRs (no two-workgroups-per-CU register cap) and factor_forward_sb (C2 strong
   // scaling at 4-8 GPUs: 256 / 128 per GPU)
-  c.sb = mode == MODE_SOLVE && !c.bounded && !c.huber && batch <= device_cus(st) &&
+  c.sb = mode == MODE_SOLVE && !c.bounded && !c.huber && !c.mhuber && batch <= device_cus(st) &&
          smem_bytes(dm, NT, false, true) + g_opt_smem_pad <= REG_LDS_LIMIT;
   // pad: mhe_set_option, occupancy A/B only; MODE_COV: the query panel on top (dp x 16)
   c.smem = smem_bytes(dm, NT, c.bounded, c.sb, mode == MODE_COV) + g_opt_smem_pad;
@@ -2604,12 +2633,34 @@ int launch_gn(const mhe_dims* dm, GnArgs& a, int batch, int mode, hipStream_t st
   if constexpr (MEAS::MIXED) {
     return MHE_ERR_UNSUPPORTED;  // mixed rows: large-system path only
   } else {
-    const GnChoice ch = gn_choice(dm, a.NT, batch, mode, st);
+    const GnChoice ch = gn_choice(dm, a.NT, batch, mode, st, a.md != nullptr);
     const bool bounded = ch.bounded, huber = ch.huber, sb = ch.sb;
     const int smem = ch.smem;
     if (smem > REG_LDS_LIMIT) return MHE_ERR_UNSUPPORTED;
     void (*kern)(GnArgs) = nullptr;
-    if (bounded) kern = huber ? k_gn_bounded<DYN, MEAS, MAX_SLOTS, true> : k_gn_bounded<DYN, MEAS, MAX_SLOTS>;
+    if (ch.mhuber) {
+      // robust measurement rows: scalar rows of a nonlinear model only have these instances
+      if constexpr (!MEAS::LINEAR && MEAS::p == 1) {
+        if (bounded)
+          kern = huber ? k_gn_bounded<DYN, MEAS, MAX_SLOTS, true, true> : k_gn_bounded<DYN, MEAS, MAX_SLOTS, false, true>;
+        else if (mode == MODE_SOLVE)
+          kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE, true, MHE_GN_MINW, false, true>
+                       : k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE, false, MHE_GN_MINW, false, true>;
+        else if (mode == MODE_ASSEMBLE)
+          kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE, true, MHE_GN_MINW, false, true>
+                       : k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE, false, MHE_GN_MINW, false, true>;
+        else if (mode == MODE_COV) {
+          if constexpr (DYN::n <= 16)
+            kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_COV, true, MHE_GN_MINW, false, true>
+                         : k_gn<DYN, MEAS, MAX_SLOTS, MODE_COV, false, MHE_GN_MINW, false, true>;
+          else
+            return MHE_ERR_UNSUPPORTED;
+        } else
+          return MHE_ERR_UNSUPPORTED;
+      } else {
+        return MHE_ERR_UNSUPPORTED;
+      }
+    } else if (bounded) kern = huber ? k_gn_bounded<DYN, MEAS, MAX_SLOTS, true> : k_gn_bounded<DYN, MEAS, MAX_SLOTS>;
     else if (mode == MODE_SOLVE)
       kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE, true>
              : sb  ? k_gn<DYN, MEAS, SB_SLOTS, MODE_SOLVE, false, 2, true>
@@ -2773,10 +2824,16 @@ inline BigAsmShape big_asm_shape(const BigArgs& A) {
 template <class DYN, class MEAS>
 inline int launch_big_resid(const BigArgs& A, int batch, int final_pass, hipStream_t st) {
   const int smem = A.P * A.n * (int)sizeof(double);
-  if (hipFuncSetAttribute((const void*)k_big_resid<DYN, MEAS>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
-      hipSuccess)
+  void (*kern)(BigArgs, int) = k_big_resid<DYN, MEAS>;
+  if (A.md) {  // robust measurement rows (meas_delta): scalar rows of a nonlinear model
+    if constexpr (!MEAS::LINEAR && MEAS::p == 1)
+      kern = k_big_resid<DYN, MEAS, true>;
+    else
+      return MHE_ERR_UNSUPPORTED;
+  }
+  if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
     return MHE_ERR_HIP;
-  hipLaunchKernelGGL((k_big_resid<DYN, MEAS>), dim3(batch), dim3(BIG_NTHREADS), smem, st, A, final_pass);
+  hipLaunchKernelGGL(kern, dim3(batch), dim3(BIG_NTHREADS), smem, st, A, final_pass);
   return MHE_OK;
 }
 
@@ -2836,10 +2893,12 @@ int launch_big(const mhe_dims* dm, BigArgs& A, int batch, int max_iter, hipStrea
     return MHE_ERR_HIP;
   const bool bounded = A.n_bounds > 0;
   const int smem_ls = A.P * A.n * (int)sizeof(double);
+  void (*k_ls)(BigArgs) = k_big_linesearch<DYN, MEAS>;
+  if constexpr (!MEAS::LINEAR && MEAS::p == 1)
+    if (A.md) k_ls = k_big_linesearch<DYN, MEAS, true>;  // the robust cost along the arc
   if (bounded) {
     if (smem_ls > 128 * 1024) return MHE_ERR_UNSUPPORTED;
-    if (hipFuncSetAttribute((const void*)k_big_linesearch<DYN, MEAS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            smem_ls) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)k_ls, hipFuncAttributeMaxDynamicSharedMemorySize, smem_ls) != hipSuccess)
       return MHE_ERR_HIP;
     const size_t nx = (size_t)batch * A.P * A.n;
     hipLaunchKernelGGL(k_big_project<DYN::n>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, A, batch);
@@ -2853,7 +2912,7 @@ int launch_big(const mhe_dims* dm, BigArgs& A, int batch, int max_iter, hipStrea
     launch_big_factor(cp, A, batch, st);
     if (K > 0) hipLaunchKernelGGL((k_big_border<DYN::n, MEAS::p>), dim3(batch), dim3(BIG_NTHREADS), smem_b, st, A);
     if (bounded)
-      hipLaunchKernelGGL((k_big_linesearch<DYN, MEAS>), dim3(batch), dim3(BIG_NTHREADS), smem_ls, st, A);
+      hipLaunchKernelGGL(k_ls, dim3(batch), dim3(BIG_NTHREADS), smem_ls, st, A);
     else
       hipLaunchKernelGGL((k_big_update<DYN::n>), dim3(batch), dim3(256), 0, st, A);
   }
@@ -2873,6 +2932,7 @@ const PairOps* pairs_vdp(int dyn, int meas);
 const PairOps* pairs_integrators(int dyn, int meas);
 const PairOps* pairs_gnss(int dyn, int meas);
 const PairOps* pairs_vehicles(int dyn, int meas);
+const PairOps* pairs_autocar(int dyn, int meas);
 const PairOps* pairs_receivers(int dyn, int meas);
 
 }  // namespace mhe

@@ -181,6 +181,7 @@ const PairOps* find_pair(const mhe_dims* dm) {
   if (!ops) ops = pairs_integrators(dm->dyn_model, dm->meas_model);
   if (!ops) ops = pairs_gnss(dm->dyn_model, dm->meas_model);
   if (!ops) ops = pairs_vehicles(dm->dyn_model, dm->meas_model);
+  if (!ops) ops = pairs_autocar(dm->dyn_model, dm->meas_model);
   if (!ops) ops = pairs_receivers(dm->dyn_model, dm->meas_model);
 #endif
   return ops;
@@ -328,6 +329,18 @@ BigArgs make_big_args(const mhe_dims* dims, const void* cbuf, int NT, void* work
   A.huber_delta = dims->huber_delta;
   A.tag = const_tag(dims, NT);
   return A;
+}
+
+// The per-solve row inputs of mhe_solve_args: Rw needs a nonlinear measurement model (a
+// linear h folds Rw into Cc), meas_delta also scalar rows (p = 1).
+int check_row_args(const mhe_dims* dims, const double* Rw, const double* meas_delta) {
+  if (!Rw && !meas_delta) return MHE_OK;
+  int p, q;
+  bool lin;
+  meas_info(dims->meas_model, dims->n, p, q, lin);
+  if (lin) return MHE_ERR_UNSUPPORTED;
+  if (meas_delta && p != 1) return MHE_ERR_UNSUPPORTED;
+  return MHE_OK;
 }
 
 }  // namespace
@@ -565,6 +578,7 @@ int mhe_gn_solve_ext(const mhe_dims* dims, const void* const_buf, int32_t batch,
   g.Y = Y; g.PAR = PAR; g.par_bstride = par_bstride; g.Rw = nullptr; g.rw_bstride = 0; g.x0 = x0;
   g.cost_out = cost_out; g.iters_out = iters_out; g.status_out = status_out; g.max_iter = max_iter; g.tol = tol;
   g.workspace = workspace; g.workspace_bytes = workspace_bytes;
+  g.meas_delta = nullptr; g.md_bstride = 0;
   return mhe_solve(dims, const_buf, &g, stream);
 }
 
@@ -581,12 +595,8 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
       (dims->M > 0 && !g->Y) || (dims->m > 0 && !g->U) || (dims->q > 0 && !g->PAR) || (dims->has_prior && !g->x0) ||
       (dims->n_extra > 0 && (!g->Z0 || !g->Z_out)))
     return MHE_ERR_NULL;
-  if (g->Rw) {  // per-solve weights: nonlinear measurement models only (a linear h folds Rw into Cc)
-    int p, q;
-    bool lin;
-    meas_info(dims->meas_model, dims->n, p, q, lin);
-    if (lin) return MHE_ERR_UNSUPPORTED;
-  }
+  rc = check_row_args(dims, g->Rw, g->meas_delta);  // per-solve weights / robust rows
+  if (rc != MHE_OK) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -594,7 +604,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
     if (!g->workspace || g->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
     BigArgs A = make_big_args(dims, const_buf, NT, g->workspace);
     A.U = g->U; A.ustride = g->u_bstride; A.Y = g->Y; A.PAR = g->PAR; A.pstride = g->par_bstride; A.x0 = g->x0;
-    A.Rw = g->Rw; A.rwstride = g->rw_bstride;
+    A.Rw = g->Rw; A.rwstride = g->rw_bstride; A.md = g->meas_delta; A.mdstride = g->md_bstride;
     A.X = g->X_out; A.cost = g->cost_out; A.iters = g->iters_out; A.state = g->status_out; A.tol = g->tol;
     A.Z = g->Z_out;
     A.lam = dims->n_eq > 0 ? g->lambda_out : nullptr;
@@ -614,6 +624,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   a.X0 = g->X0; a.Xout = g->X_out; a.U = g->U; a.ustride = g->u_bstride; a.Y = g->Y; a.PAR = g->PAR;
   a.pstride = g->par_bstride; a.x0 = g->x0; a.cost = g->cost_out; a.iters = g->iters_out; a.status = g->status_out;
   a.max_iter = g->max_iter; a.tol = g->tol; a.Rw = g->Rw; a.rwstride = g->rw_bstride;
+  a.md = g->meas_delta; a.mdstride = g->md_bstride;
   return ops->gn(dims, a, batch, MODE_SOLVE, st);
 }
 
@@ -646,12 +657,8 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
   if (!const_buf || !at->X0 || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) || (dims->q > 0 && !at->PAR) ||
       (dims->has_prior && !at->x0))
     return MHE_ERR_NULL;
-  if (at->Rw) {  // as mhe_solve: a linear h folds Rw into the constants
-    int p, q;
-    bool lin;
-    meas_info(dims->meas_model, dims->n, p, q, lin);
-    if (lin) return MHE_ERR_UNSUPPORTED;
-  }
+  rc = check_row_args(dims, at->Rw, at->meas_delta);  // as mhe_solve
+  if (rc != MHE_OK) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -661,7 +668,7 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
     BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
     A.n_bounds = 0;  // the unconstrained GN model at X (bounds are not reflected)
     A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
-    A.Rw = at->Rw; A.rwstride = at->rw_bstride;
+    A.Rw = at->Rw; A.rwstride = at->rw_bstride; A.md = at->meas_delta; A.mdstride = at->md_bstride;
     A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
     A.cost = (double*)scratch; A.state = status_out;
     A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
@@ -674,7 +681,8 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
   }
   GnArgs a = make_args(dims, const_buf, NT);
   a.X0 = at->X0; a.U = at->U; a.ustride = at->u_bstride; a.Y = at->Y; a.PAR = at->PAR; a.pstride = at->par_bstride;
-  a.x0 = at->x0; a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.status = status_out;
+  a.x0 = at->x0; a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.md = at->meas_delta; a.mdstride = at->md_bstride;
+  a.status = status_out;
   a.PhiQ = PhiQ; a.nq = n_query; a.cov = cov_out;
   return ops->gn(dims, a, batch, MODE_COV, st);
 }
@@ -704,9 +712,11 @@ int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const
   return ops->resjac(a, batch, (hipStream_t)stream);
 }
 
-int mhe_assemble(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
-                 int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
-                 double* H, double* g, double* cost, void* stream) {
+// mhe_assemble with the per-solve row inputs (mhe_assemble_at); the positional call passes none
+static int assemble_reg(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
+                        int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
+                        const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride, double* H,
+                        double* g, double* cost, void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
@@ -720,7 +730,15 @@ int mhe_assemble(const mhe_dims* dims, const void* const_buf, int32_t batch, con
   GnArgs a = make_args(dims, const_buf, NT);
   a.X0 = X; a.U = U; a.ustride = u_bstride; a.Y = Y; a.PAR = PAR; a.pstride = par_bstride; a.x0 = x0;
   a.Hout = H; a.gout = g; a.cost = cost;
+  a.Rw = Rw; a.rwstride = rw_bstride; a.md = md; a.mdstride = md_bstride;
   return ops->gn(dims, a, batch, MODE_ASSEMBLE, (hipStream_t)stream);
+}
+
+int mhe_assemble(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
+                 int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
+                 double* H, double* g, double* cost, void* stream) {
+  return assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0, H, g,
+                      cost, stream);
 }
 
 int mhe_chol_solve(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,
@@ -760,7 +778,7 @@ int32_t mhe_solve_kernel_name(const mhe_dims* dims, int32_t batch, void* stream,
              dims->n_bounds > 0 ? "linesearch" : "update");
     return MHE_OK;
   }
-  const GnChoice c = gn_choice(dims, NT, batch, MODE_SOLVE, (hipStream_t)stream);
+  const GnChoice c = gn_choice(dims, NT, batch, MODE_SOLVE, (hipStream_t)stream);  // a call without meas_delta
   if (c.smem > REG_LDS_LIMIT) return MHE_ERR_UNSUPPORTED;
   snprintf(buf, len, "mhe::%s<dyn %d, meas %d, SLOTS=%d, MODE_SOLVE, HUBER=%d%s>%s", c.bounded ? "k_gn_bounded" : "k_gn",
            dims->dyn_model, dims->meas_model, c.sb ? SB_SLOTS : MAX_SLOTS, c.huber ? 1 : 0,
@@ -792,16 +810,21 @@ int32_t mhe_kkt_dim(const mhe_dims* dims) {
   return dp < 0 ? dp : dp + dims->n_extra + dims->n_eq;
 }
 
-int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
+// mhe_assemble_kkt_ws with the per-solve row inputs (mhe_assemble_at); the positional call passes none
+static int assemble_kkt(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
                         const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
-                        const double* x0, double* H, double* g, double* cost, int32_t* status, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+                        const double* x0, const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride,
+                        double* H, double* g, double* cost, int32_t* status, void* workspace, size_t workspace_bytes,
+                        void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
+  rc = check_row_args(dims, Rw, md);
+  if (rc != MHE_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!is_big(dims)) {
-    rc = mhe_assemble(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, H, g, cost, stream);
+    rc = assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, Rw, rw_bstride, md, md_bstride,
+                      H, g, cost, stream);
     if (rc == MHE_OK && status && batch > 0 && hipMemsetAsync(status, 0, sizeof(int32_t) * batch, st) != hipSuccess)
       return MHE_ERR_HIP;
     return rc;
@@ -816,6 +839,7 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
   BigArgs A = make_big_args(dims, const_buf, NT, workspace);
   A.n_bounds = 0;  // the plain GN system: the projected method's reduction belongs to the solve
   A.U = U; A.ustride = u_bstride; A.Y = Y; A.PAR = PAR; A.pstride = par_bstride; A.x0 = x0;
+  A.Rw = Rw; A.rwstride = rw_bstride; A.md = md; A.mdstride = md_bstride;
   A.X = const_cast<double*>(X);  // read only by k_big_resid / k_big_assemble
   A.Z = const_cast<double*>(Z);  // read only by k_big_resid
   A.cost = cost; A.state = status;
@@ -831,6 +855,26 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
   if (K > 0) hipLaunchKernelGGL(k_big_export_border, dim3(K, batch), dim3(256), 0, st, A, batch, dims->p, H, g);
   hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status);
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
+int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
+                        const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
+                        const double* x0, double* H, double* g, double* cost, int32_t* status, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  return assemble_kkt(dims, const_buf, batch, X, Z, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0, H, g,
+                      cost, status, workspace, workspace_bytes, stream);
+}
+
+int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, double* H, double* g,
+                    double* cost, int32_t* status, void* stream) {
+  int NT = 0;
+  const int rc = check_dims(dims, &NT);
+  if (rc != MHE_OK) return rc;
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  return assemble_kkt(dims, const_buf, at->batch, at->X0, at->Z0, at->U, at->u_bstride, at->Y, at->PAR,
+                      at->par_bstride, at->x0, at->Rw, at->rw_bstride, at->meas_delta, at->md_bstride, H, g, cost,
+                      status, at->workspace, at->workspace_bytes, stream);
 }
 
 int mhe_chol_solve_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,

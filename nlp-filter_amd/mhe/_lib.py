@@ -56,7 +56,7 @@ class MheSolveArgs(_Sized):
                 ("U", c_vp), ("u_bstride", c_i64), ("Y", c_vp), ("PAR", c_vp), ("par_bstride", c_i64),
                 ("Rw", c_vp), ("rw_bstride", c_i64), ("x0", c_vp), ("cost_out", c_vp), ("iters_out", c_vp),
                 ("status_out", c_vp), ("max_iter", c_i32), ("tol", c_dbl), ("workspace", c_vp),
-                ("workspace_bytes", c_sz), ("lambda_out", c_vp)]
+                ("workspace_bytes", c_sz), ("lambda_out", c_vp), ("meas_delta", c_vp), ("md_bstride", c_i64)]
 
 
 _P = ctypes.POINTER(MheDims)
@@ -89,6 +89,7 @@ SIGNATURES = {
     "mhe_big_envelope": (c_i32, [_P, c_vp, c_sz, c_i32, c_vp, c_i32, c_vp]),
     "mhe_assemble_kkt_ws": (ctypes.c_int, [_P, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mhe_assemble_at": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mhe_cov_scratch_bytes": (c_sz, [_P, c_i32, c_i32]),
     "mhe_state_cov": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
                                      c_vp]),

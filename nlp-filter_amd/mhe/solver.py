@@ -294,9 +294,35 @@ class BatchSolver:
             raise ValueError(f"Rw must be (B|1,) + {shape}, got {tuple(t.shape)}")
         return t, (0 if t.shape[0] == 1 else int(np.prod(shape)))
 
+    def _md(self, meas_delta, B):
+        """Pseudo-Huber scales of the measurement rows (mhe_solve_args.meas_delta): (B|1, M)
+        or (M,), float64, every value > 0 (+inf = a quadratic row); None = quadratic rows."""
+        if meas_delta is None:
+            return None, 0
+        if self.linear_meas:
+            raise ValueError("meas_delta needs a nonlinear measurement model (a linear h folds R into the constants)")
+        if self.p != 1:
+            raise ValueError("meas_delta needs scalar measurement rows (p = 1)")
+        if isinstance(meas_delta, torch.Tensor):
+            if meas_delta.dtype != torch.float64:
+                raise ValueError(f"meas_delta must be float64, got {meas_delta.dtype}")
+        else:
+            meas_delta = np.asarray(meas_delta)
+            if meas_delta.dtype != np.float64:
+                raise ValueError(f"meas_delta must be float64, got {meas_delta.dtype}")
+        t = _dev(meas_delta, self.device)
+        if t.dim() == 1:
+            t = t[None]
+        if t.dim() != 2 or t.shape[1] != self.M or t.shape[0] not in (1, B):
+            raise ValueError(f"meas_delta must be (B|1, {self.M}) or ({self.M},), got {tuple(t.shape)}")
+        if not bool((t > 0).all()):  # NaN fails the comparison too
+            raise ValueError("meas_delta must be > 0 (+inf = quadratic row)")
+        return t, (0 if t.shape[0] == 1 else self.M)
+
     def _gn(self, s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
-            Z=None, Zo=None, Rw=None, lam=None):
+            Z=None, Zo=None, Rw=None, lam=None, meas_delta=None):
         Rw_t, rstr = self._rw(Rw, B)
+        md_t, mstr = self._md(meas_delta, B)
         if B == 0:
             return
         chunk = self._chunk(B, s)
@@ -326,18 +352,22 @@ class BatchSolver:
             a.max_iter, a.tol = int(max_iter), float(tol)
             a.workspace, a.workspace_bytes = (None if ws is None else ctypes.c_void_p(ws.data_ptr())), nb
             a.lambda_out = at(lam, self.n_eq)
+            a.meas_delta, a.md_bstride = at(md_t, 0, mstr), mstr
             rc = self.lib.mhe_solve(self.dims, _ptr(self.cbuf), ctypes.byref(a), _handle(s))
             _lib.check(rc, "mhe_solve")
-        keep_alive(s, cur, X, Xo, Z, Zo, U_t, Y_t, PAR_t, Rw_t, x0_t, cost, iters, status, ws, lam)
+        keep_alive(s, cur, X, Xo, Z, Zo, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, cost, iters, status, ws, lam)
 
     # ------------------------------------------------------------------ calls
     def solve(self, X0, U, Y, PAR=None, x0=None, max_iter=20, tol=1e-10, stream=None, out=None, Z0=None, Rw=None,
-              lam_out=None):
+              lam_out=None, meas_delta=None):
         """Gauss-Newton to convergence. Returns (X, cost, iters, status) device tensors,
         and the extra variables Z (B, n_extra) as a fifth element when n_extra > 0.
         ``Rw`` (B|1, M, p, p) -- (B|1, M) for mixed rows -- replaces the measurement
         weights of the constants for this solve (nonlinear models; the MHE windows'
-        R = 0 slot masks).  With ``stream`` the work (staging included) is ordered on
+        R = 0 slot masks).  ``meas_delta`` (B|1, M) or (M,), float64, > 0: the pseudo-Huber
+        scale of every (scalar) measurement row, in the row's units -- the reference's
+        pseudo_huber_loss with Q = R_i, solved by IRLS; +inf keeps a row quadratic, ``cost`` is
+        the robust objective (nonlinear models with p = 1).  With ``stream`` the work (staging included) is ordered on
         that stream; consume the outputs there or make the consuming stream wait for it.
         ``lam_out`` (B, n_eq) float64 device tensor: receives this solve's constraint
         multipliers (the per-call way; ``self.lam`` is the last solve's on any stream,
@@ -366,7 +396,7 @@ class BatchSolver:
                 else:
                     lam = torch.zeros((B, self.n_eq), dtype=torch.float64, device=self.device)
             self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol, Z, Zo,
-                     Rw, lam)
+                     Rw, lam, meas_delta)
             self.lam = lam
         if self.n_extra:
             return Xo, cost, iters, status, Zo
@@ -376,12 +406,13 @@ class BatchSolver:
         """Pre-stage device inputs once (bench: inputs resident before timing)."""
         return self._inputs(X0, U, Y, PAR, x0)
 
-    def solve_staged(self, staged, outs, max_iter, tol, stream=None):
+    def solve_staged(self, staged, outs, max_iter, tol, stream=None, meas_delta=None):
         X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = staged
         Xo, cost, iters, status = outs
         self._check_ready()
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol)
+            self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
+                     meas_delta=meas_delta)
 
     def resjac(self, X, U, Y, PAR=None, stream=None):
         """Per-node defects W (B,P,n) and dynamics Jacobians F (B,P,n,n), per-row
@@ -407,13 +438,15 @@ class BatchSolver:
         border rows for a bordered (KKT) problem (mhe_kkt_dim)."""
         return self.lib.mhe_kkt_dim(self.dims)
 
-    def assemble(self, X, U, Y, PAR=None, x0=None, stream=None, status_out=False, Z=None):
+    def assemble(self, X, U, Y, PAR=None, x0=None, stream=None, status_out=False, Z=None, Rw=None, meas_delta=None):
         """GN normal equations at X: H (B,dp,dp), g (B,dp), cost (B) -- dense, node-major
         (row j*n + c; padding nodes last) on both paths.  The large-system path runs the
         solve's own k_big_resid + k_big_assemble over a workspace (mhe_assemble_kkt_ws) and
         copies H out of their component-major tiles.  A bordered problem (n_extra / n_eq
         > 0) returns the KKT system of kkt_dim rows instead (H_xz, H_zz, the constraint
-        rows; g = [g_x; g_z; C v - r]) at (X, Z).  ``status_out``: also return the
+        rows; g = [g_x; g_z; C v - r]) at (X, Z).  ``Rw`` / ``meas_delta`` as for solve():
+        the system a solve with them forms at X (mhe_assemble_at; with ``meas_delta`` the IRLS
+        weights at X and the robust cost).  ``status_out``: also return the
         per-trajectory status (0, or 4 = constants built for other dims)."""
         self._check_ready()
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
@@ -431,21 +464,39 @@ class BatchSolver:
             chunk = max(1, self._chunk(B, s))
             ws, nb = self._workspace(chunk, s)
             P, n, M = self.P, self.n, self.M
+            Rw_t, rstr = self._rw(Rw, B)
+            md_t, mstr = self._md(meas_delta, B)
             for lo in range(0, B, chunk):
                 c = min(chunk, B - lo)
+                if Rw_t is not None or md_t is not None:
+                    a = _lib.MheSolveArgs()
+                    a.batch = c
+                    a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, self.n_extra)
+                    a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
+                    a.Y = _at(Y_t, lo, M * self.p)
+                    a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
+                    a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
+                    a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
+                    a.x0 = _at(x0_t, lo, n)
+                    a.workspace, a.workspace_bytes = _ptr(ws), nb
+                    rc = self.lib.mhe_assemble_at(self.dims, _ptr(self.cbuf), ctypes.byref(a), _at(H, lo, dk * dk),
+                                                  _at(g, lo, dk), _at(cost, lo, 1), _at(status, lo, 1, 4), _handle(s))
+                    _lib.check(rc, "mhe_assemble_at")
+                    continue
                 rc = self.lib.mhe_assemble_kkt_ws(
                     self.dims, _ptr(self.cbuf), c, _at(X, lo, P * n), _at(Z_t, lo, self.n_extra), _at(U_t, lo, ustr),
                     ustr, _at(Y_t, lo, M * self.p), _at(PAR_t, lo, pstr), pstr, _at(x0_t, lo, n), _at(H, lo, dk * dk),
                     _at(g, lo, dk), _at(cost, lo, 1), _at(status, lo, 1, 4), _ptr(ws), nb, _handle(s))
                 _lib.check(rc, "mhe_assemble_kkt_ws")
-            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, x0_t, H, g, cost, status, ws)
+            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, H, g, cost, status, ws)
         if status_out:
             return H, g, cost, status
         return H, g, cost
 
-    def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None):
+    def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None, meas_delta=None):
         """Posterior covariance of the state at query times (mhe_state_cov): with H = J^T W J
-        at X (the solve's own assembly: Huber weights, per-solve ``Rw``) and S_t = phi(t)^T (x)
+        at X (the solve's own assembly: Huber weights, per-solve ``Rw``, the IRLS weights of
+        ``meas_delta`` at X) and S_t = phi(t)^T (x)
         I_n, cov[b, q] = S_t H^-1 S_t^T, from the solve's Cholesky factor by a forward sweep
         of the query columns.  Query times ``t`` (Tq,) in [0, T] go through the Lagrange basis
         extractSolution uses; or pass the basis rows ``Phi`` (Tq, P) directly.  Returns
@@ -467,6 +518,7 @@ class BatchSolver:
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
             X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
             Rw_t, rstr = self._rw(Rw, B)
+            md_t, mstr = self._md(meas_delta, B)
             PhiQ = _dev(Phi, self.device)
             n, P, M = self.n, self.P, self.M
             cov = torch.empty((B, Tq, n, n), dtype=torch.float64, device=self.device)
@@ -485,13 +537,14 @@ class BatchSolver:
                 a.Y = _at(Y_t, lo, M * self.p)
                 a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
                 a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
+                a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
                 a.x0 = _at(x0_t, lo, n)
                 a.workspace, a.workspace_bytes = _ptr(ws), nb
                 rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
                                             _at(cov, lo, Tq * n * n), _at(status, lo, 1, 4), _ptr(scratch), sb,
                                             _handle(s))
                 _lib.check(rc, "mhe_state_cov")
-            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, x0_t, PhiQ, cov, status, ws, scratch)
+            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, PhiQ, cov, status, ws, scratch)
         return cov, status
 
     def chol_solve(self, H, g, stream=None):

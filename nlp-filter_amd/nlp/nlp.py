@@ -21,6 +21,10 @@ Kept semantics
     missing name or before ``solve()`` (nlp/nlp.py:85-119)
 
   * ``pseudo_huber_loss`` dynamics cost (cost_functions.py:25-31) -> IRLS on the GPU
+  * ``addResidualCost(..., cost_function=pseudo_huber_loss, cost_params={"delta": d})``
+    (keyword-only additions to the reference's signature): pseudo_huber_loss with Q = R on
+    that call's scalar measurement rows -> IRLS weights per row on the GPU
+    (mhe_solve_args.meas_delta); ``solver["objective"]`` is then the robust objective
   * ``addVarBounds`` on the state trajectory -> projected Newton on the GN model
     (epsilon-active set, reduced step, Armijo search along the projection arc: the
     solution is a KKT point); bounds on other variables are checked after the solve
@@ -278,13 +282,37 @@ class fixedTimeOptimalEstimationNLP(NLP):
                                      "pseudo_huber_loss")
         self._dyn_cost = Qw
 
-    def addResidualCost(self, measurement_model, X, t_array, y_array, R, params=None):
-        """nlp/nlp.py:247-277: sum_i r_i^T R r_i, r_i = y_i - h(x(t_i), params)."""
+    def addResidualCost(self, measurement_model, X, t_array, y_array, R, params=None, *, cost_function=None,
+                        cost_params=None):
+        """nlp/nlp.py:247-277: sum_i r_i^T R r_i, r_i = y_i - h(x(t_i), params).
+
+        ``cost_function=cost_functions.pseudo_huber_loss`` with ``cost_params={"delta": d}``
+        (not in the reference's signature, hence keyword-only) puts the pseudo-Huber loss
+        with Q = R on this call's rows instead: 2 R d^2 (sqrt(1 + r^2 / d^2) - 1) per scalar
+        row, d in the row's units.  R stays the weight (a "Q" entry is refused).  Rows of
+        other calls stay quadratic."""
+        delta = np.inf
+        if cost_function is not None:
+            name = _fname(cost_function)
+            if name != "pseudo_huber_loss":
+                raise UnsupportedFeature(f"measurement cost {name!r}: supported is pseudo_huber_loss "
+                                         "(default: the quadratic r^T R r)")
+            cost_params = cost_params or {}
+            if "Q" in cost_params:
+                raise UnsupportedFeature("pseudo_huber_loss on measurement rows: R is the weight, "
+                                         "cost_params takes only 'delta'")
+            if "delta" not in cost_params:
+                raise ValueError("pseudo_huber_loss needs cost_params={'delta': ...}")
+            delta = float(_resolve(cost_params["delta"]))
+            if not delta > 0.0:
+                raise ValueError(f"pseudo_huber_loss delta must be > 0, got {delta}")
+        elif cost_params is not None:
+            raise ValueError("cost_params without cost_function")
         t_array = np.asarray(t_array, dtype=np.float64).reshape(-1)
         M_i = t_array.shape[0]
         p = y_array.shape[0] if y_array is not None else int(params["p"])
         Y = self.addParameter(M_i, p)
-        self._meas.append(dict(h=measurement_model, t=t_array, Y=Y, R=R, params=params or {}, p=p))
+        self._meas.append(dict(h=measurement_model, t=t_array, Y=Y, R=R, params=params or {}, p=p, delta=delta))
         if y_array is not None:
             self.setMeasurement(Y, t_array, y_array)
         return Y
@@ -412,7 +440,7 @@ class fixedTimeOptimalEstimationNLP(NLP):
 
     def _mixed_rows(self, zoff):
         """MHE_MEAS_MIXED encoding (include/mhe.h) of every addResidualCost term:
-        (t (M,), rows (M,14), Rw (M,), Y (M,)), sorted by time (stable) so that
+        (t (M,), rows (M,14), Rw (M,), Y (M,), delta (M,)), sorted by time (stable) so that
         rows at one time form one epoch on the device."""
         n = self.n
 
@@ -425,7 +453,7 @@ class fixedTimeOptimalEstimationNLP(NLP):
                 return [n + zoff[id(y)] + c for c in range(k)], np.zeros(k)
             return [-1] * k, vec(y, k)
 
-        t_all, rows, Rw, Yv = [], [], [], []
+        t_all, rows, Rw, Yv, dl = [], [], [], [], []
         for g in self._meas:
             name, par, p = _fname(g["h"]), g["params"], g["p"]
             R = np.asarray(_resolve(g["R"]), dtype=np.float64).reshape(p, p)
@@ -474,9 +502,11 @@ class fixedTimeOptimalEstimationNLP(NLP):
                     rows.append(np.concatenate([np.asarray(ids, dtype=np.float64), v]))
                     Rw.append(w)
                     Yv.append(yi[r] if len(proto) > 1 else yi[0])
+                    dl.append(g["delta"])
         t_all = np.asarray(t_all)
         order = np.argsort(t_all, kind="stable")
-        return t_all[order], np.stack(rows)[order], np.asarray(Rw)[order], np.asarray(Yv)[order]
+        return (t_all[order], np.stack(rows)[order], np.asarray(Rw)[order], np.asarray(Yv)[order],
+                np.asarray(dl, dtype=np.float64)[order])
 
     def _spec(self):
         if self._dyn is None:
@@ -552,6 +582,12 @@ class fixedTimeOptimalEstimationNLP(NLP):
         from mhe import solver as _solver
         if self._dyn is None or self._dyn_cost is None or not self._meas:
             self._spec()  # raises the precise error
+        if (not self._is_general() and _fname(self._meas[0]["h"]) == "full_state"
+                and any(np.isfinite(g["delta"]) for g in self._meas)):
+            # a linear h has R folded into the device constants: no per-row reweighting there
+            raise UnsupportedFeature("pseudo_huber_loss on a pure full_state problem is not supported (R is part of "
+                                     "the device constants); mixed problems carry full_state as COMPONENT rows, "
+                                     "which do support it")
         self._verify_plugins()
         func = self._dyn[0]
         dname = _fname(func)
@@ -568,11 +604,12 @@ class fixedTimeOptimalEstimationNLP(NLP):
             if nz > 4:
                 raise UnsupportedFeature(f"{nz} extra decision variables (at most 4 on the GPU path)")
             zoff = {id(v): off for v, off in extra}
-            t_meas, rows, Rw, Yv = self._mixed_rows(zoff)
+            t_meas, rows, Rw, Yv, dl = self._mixed_rows(zoff)
             mname, idx, PAR = "mixed", None, rows
             self._Ymixed = Yv
         else:
             mname, t_meas, Rw, PAR, idx = self._spec()
+            dl = np.concatenate([np.full(len(g["t"]), g["delta"], dtype=np.float64) for g in self._meas])
             self._Ymixed = None
         Phi = self.CPM.lagrange_matrix(t_meas)
         # R enters the device constants only for a linear h (folded into J^T W J); a
@@ -590,6 +627,7 @@ class fixedTimeOptimalEstimationNLP(NLP):
             self._engine_key = key
             self.engine_builds = getattr(self, "engine_builds", 0) + 1
         self._Rw_solve = None if linear else Rw
+        self._md_solve = dl if np.any(np.isfinite(dl)) else None  # per-row pseudo-Huber scales (per solve)
         self._PAR = PAR
         self._extra = extra
 
@@ -707,9 +745,11 @@ class fixedTimeOptimalEstimationNLP(NLP):
         lam_t = None
         if eng.n_eq:
             lam_t = torch.empty((1, eng.n_eq), dtype=torch.float64, device=eng.device)
-        out = eng.solve(X0, U, Y, PAR, x0, max_iter=self.max_iter, tol=self.tol, Z0=Z0, Rw=Rw, lam_out=lam_t)
+        md = None if self._md_solve is None else self._md_solve[None]
+        out = eng.solve(X0, U, Y, PAR, x0, max_iter=self.max_iter, tol=self.tol, Z0=Z0, Rw=Rw, lam_out=lam_t,
+                        meas_delta=md)
         X, cost, iters, status = out[:4]
-        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, engine=eng)  # extractCovariance
+        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, md=md, engine=eng)  # extractCovariance
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         X = X.cpu().numpy()[0]
@@ -738,7 +778,8 @@ class fixedTimeOptimalEstimationNLP(NLP):
     def extractCovariance(self, name, t_array):
         """Posterior covariance (T, n, n) of the last solve's state estimate at the times
         ``t_array`` -- what extractSolution returns the mean of: S_t (J^T W J)^-1 S_t^T at
-        the solution, with that solve's controls, measurements, prior and R
+        the solution, with that solve's controls, measurements, prior, R and -- for
+        pseudo-Huber measurement rows -- their IRLS weights at the solution
         (BatchSolver.covariance).  A covariance when Q, R and the prior weight are inverse
         covariances; e.g. ``inv(extractCovariance("x", [DT])[0])`` is the arrival-cost weight
         of the next window.  State bounds are not reflected.  Raises UnsupportedFeature for
@@ -757,7 +798,8 @@ class fixedTimeOptimalEstimationNLP(NLP):
         import torch
         X = np.stack([x.value for x in self._X])[None]
         Phi = self.CPM.lagrange_matrix(np.asarray(t_array, dtype=np.float64).reshape(-1))
-        cov, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"])
+        cov, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"],
+                                     meas_delta=last["md"])
         torch.cuda.synchronize()
         st = int(status.cpu().numpy()[0])
         if st != 0:

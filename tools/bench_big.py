@@ -1,6 +1,10 @@
 """Large-system path timing (tools only): C3 / C4 / C5 shapes of BASELINE.json.
 
-    python tools/bench_big.py [C3|C4|C5] [B] [iters]
+    python tools/bench_big.py [C3|C4|C5] [B] [iters] [meas_delta]
+
+meas_delta (optional, a scale in the rows' units): the same solve with pseudo-Huber
+measurement rows (mhe_solve_args.meas_delta, one shared (M,) array) -- the cost of the
+per-row reweighting against the run without it.
 
 GN collocation-point updates/s = B * P * iters / device time (HIP events around one
 mhe_solve call with tol = 0, inputs resident; a batch whose workspace exceeds the free
@@ -29,6 +33,7 @@ from mhe import configs, solver  # noqa: E402
 cfg = sys.argv[1] if len(sys.argv) > 1 else "C3"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 it = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+meas_delta = float(sys.argv[4]) if len(sys.argv) > 4 else None
 w = configs.CONFIGS[cfg](B=B)
 s = solver.from_workload(w)
 P, n = w.P, w.n
@@ -59,10 +64,11 @@ def nnz_g_sum():
 
 F = d ** 3 / 3 + 2 * d * d + nnz_g_sum() * P * P + 2 * P * P * n * n + 4 * P * n ** 3
 Z0 = getattr(w, "Z_init", None)
+KW = {} if meas_delta is None else {"meas_delta": torch.full((w.M,), meas_delta, dtype=torch.float64, device=s.device)}
 
 
 def run(k):
-    return s.solve(w.X_init, w.U, w.Y, w.PAR, max_iter=k, tol=0.0, Z0=Z0)
+    return s.solve(w.X_init, w.U, w.Y, w.PAR, max_iter=k, tol=0.0, Z0=Z0, **KW)
 
 
 run(1)
@@ -104,7 +110,7 @@ def envelope_share():
 
 share, fenv = envelope_share()
 Fx = F - d ** 3 / 3 + share * d ** 3 / 3
-res = {"config": cfg, "workload": w.name, "B": B, "iters": it, "d": d, "P": P, "n": n, "E": int(E),
+res = {"config": cfg, "workload": w.name, "B": B, "iters": it, "meas_delta": meas_delta, "d": d, "P": P, "n": n, "E": int(E),
        "ms_per_iter": dt / it * 1e3, "pt_updates_per_s": B * P * it / dt,
        "mflop_per_traj_iter": F / 1e6, "achieved_tflops": F * B * it / dt / 1e12,
        "frac_fp64_peak": F * B * it / dt / 1e12 / 78.6,

@@ -8,7 +8,7 @@ NAME=$1; VFLAGS=$2
 B=/tmp/mhe_variant_$NAME
 mkdir -p $B
 FLAGS="-O3 --offload-arch=gfx950 -std=c++17 -fPIC -I$ROOT/include -I$ROOT/nlp-filter_amd/csrc $VFLAGS"
-for s in mhe_gn pair_vdp pair_integrators pair_gnss pair_vehicles pair_receivers mhe_ekf mhe_ls; do
+for s in mhe_gn pair_vdp pair_integrators pair_gnss pair_vehicles pair_autocar pair_receivers mhe_ekf mhe_ls; do
   /opt/rocm/bin/hipcc $FLAGS -c -o $B/$s.o $ROOT/nlp-filter_amd/csrc/$s.hip &
 done
 wait

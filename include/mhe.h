@@ -111,7 +111,7 @@ extern "C" {
  * the size queries) unless it equals this build's sizeof -- a binding that
  * declares an older or truncated struct is refused before any later field is
  * read.  (mhe/_lib.py sets it in the ctypes constructors.) */
-#define MHE_ABI_VERSION 9
+#define MHE_ABI_VERSION 10
 
 typedef struct mhe_dims {
   int32_t struct_size;  /* = sizeof(mhe_dims)                                */
@@ -306,6 +306,20 @@ int mhe_gn_solve_ext(const mhe_dims* dims, const void* const_buf, int32_t batch,
  * weights at X) and mhe_assemble_at honour it; cost_out is the robust objective.  A linear
  * measurement model (MHE_MEAS_FULL_STATE: R is folded into the constants) and p > 1 return
  * MHE_ERR_UNSUPPORTED.  NULL: every call runs exactly the kernels it ran before v9.
+ *
+ * Per-solve prior weight (ABI v10).  Pw (B|1, n, n) is the weight of the addInitialCost term
+ * (x(0) - x0)^T Pw (x(0) - x0) for THIS call, per trajectory: a moving-horizon estimator's
+ * arrival cost changes every window and differs between the trajectories of a batch, while
+ * the constants buffer stays one for all of them (mhe_arrival below forms the next window's
+ * weight on the device).  It needs dims->has_prior == 1 (MHE_ERR_UNSUPPORTED otherwise, as
+ * for n > 16 on the register-resident path, which has no such model) and
+ * symmetric blocks (the host wrappers check that, these entry points do NOT).  Unlike Rw it
+ * works for every measurement model: the prior touches the node-0 block of J^T W J alone.
+ * The register-resident kernels add Pw_b - Pw_const to the block the constants carry, so a
+ * caller that always passes Pw should build the constants with Pw = 0 (no cancellation of
+ * two large weights).  Honoured by mhe_solve (every mode: Huber, meas_delta, bounds and their
+ * Armijo cost, bordered and mixed problems), mhe_assemble_at, mhe_state_cov and mhe_arrival;
+ * mhe_gn_solve* pass NULL.  NULL: bitwise the results of a build without the field.
  */
 typedef struct mhe_solve_args {
   int32_t struct_size;     /* = sizeof(mhe_solve_args) */
@@ -321,6 +335,12 @@ typedef struct mhe_solve_args {
   int64_t par_bstride;
   const double* Rw;        /* optional, see above */
   int64_t rw_bstride;
+  const double* Pw;        /* optional (B|1, n, n): prior (arrival-cost) weight of this solve, overriding
+                              the Pw the constants were built with (ABI v10, see "Per-solve prior
+                              weight" above); NULL = the constants'.  Beside the other per-solve
+                              weight; the struct_size check refuses every older binding wherever a
+                              field is added */
+  int64_t pw_bstride;      /* n*n, or 0 = shared by the batch */
   const double* x0;
   double* cost_out;
   int32_t* iters_out;
@@ -453,7 +473,7 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
 
 /* mhe_assemble_kkt_ws taking the struct (ABI v9): the kernel-level view of the per-solve
  * inputs the positional mhe_assemble* calls cannot carry.  at->X0 is the point (B, P, n);
- * Z0 (n_extra > 0), U, Y, PAR, Rw, meas_delta, x0 with their strides, batch and (large-
+ * Z0 (n_extra > 0), U, Y, PAR, Rw, meas_delta, Pw (ABI v10), x0 with their strides, batch and (large-
  * system path) workspace / workspace_bytes are read from the struct; its outputs and
  * max_iter / tol are not.  H, g, cost, status as mhe_assemble_kkt_ws: with meas_delta the
  * IRLS system at X (the weights lambda_i above) and the robust cost. */
@@ -477,7 +497,7 @@ int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve
  * projected quantity), as does n > 16 on the register-resident path, and a problem
  * whose query panel (dp x 16 doubles of LDS on top of the solve's) does not fit.
  *
- *   at          batch; X0 = the point (B, P, n); U, Y, PAR, x0, Rw, meas_delta and their strides, and
+ *   at          batch; X0 = the point (B, P, n); U, Y, PAR, x0, Rw, meas_delta, Pw and their strides, and
  *               on the large-system path workspace / workspace_bytes, as for mhe_solve.
  *               The outputs and max_iter / tol of the struct are not read.
  *   PhiQ        (n_query, P) DEVICE: Lagrange basis rows at the query times
@@ -492,6 +512,29 @@ size_t mhe_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_quer
 int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at,
                   const double* PhiQ, int32_t n_query, double* cov_out, int32_t* status_out,
                   void* scratch, size_t scratch_bytes, void* stream);
+
+/* Arrival cost of the next window (ABI v10): the prior a moving-horizon estimator carries
+ * from this window to the one shifted by t (the reference's loop, autonomous-car.py:232-271,
+ * with the weight the covariance gives), formed on the device for the whole batch:
+ *   x_arr   (B, n)     x(t) = sum_j phi_j X_j, summed in node order      (next prior mean)
+ *   Pw_arr  (B, n, n)  inv(S_t H^-1 S_t^T), bitwise symmetric            (next prior weight)
+ *   cov_out (B, n, n)  optional: the covariance block S_t H^-1 S_t^T itself (bitwise the
+ *                      block of mhe_state_cov for the same query), or NULL
+ * so that the next mhe_solve takes x0 = x_arr and Pw = Pw_arr without a copy.  The covariance
+ * stage is mhe_state_cov's with n_query = 1 (phi: its Lagrange row (1, P), DEVICE): the same
+ * `at` semantics (the per-solve Rw, meas_delta and Pw of the window included), the same
+ * refusals (bordered and mixed problems, n > 16 on the register-resident path, a query panel
+ * that does not fit) and the same scratch (mhe_arrival_scratch_bytes; 0 on the register
+ * path).  Then one wavefront per trajectory inverts the n x n block in LDS: Cholesky
+ * C = L L^T with true square roots and divisions, A = L^-T L^-1 written from the upper
+ * triangle.  status_out (B): 0, MHE_STATUS_NOT_SPD (a bad pivot in H or in the n x n block)
+ * or MHE_STATUS_BAD_CONSTANTS; where it is non-zero x_arr, Pw_arr and cov_out of that
+ * trajectory are NaN and no other trajectory is affected.  Only enqueues work on `stream`;
+ * allocates nothing. */
+size_t mhe_arrival_scratch_bytes(const mhe_dims* dims, int32_t batch);
+int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
+                double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
+                size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Batched extended Kalman filter.

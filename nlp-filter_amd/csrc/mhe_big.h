@@ -167,11 +167,20 @@ struct BigArgs {
   double* cov_scratch;
   const double* md;  // pseudo-Huber scale per measurement row (B|1, M) or NULL (mhe_solve_args.meas_delta)
   long long mdstride;
+  const double* Pw;  // per-solve prior weight (B|1, n, n) or NULL = the constants' Pw (mhe_solve_args.Pw)
+  long long pwstride;
 };
 
 // measurement weights of trajectory b: the per-solve array when given, else the constants'
 __device__ __forceinline__ const double* big_rw(const BigArgs& a, const double* Rc, int b) {
   return a.Rw ? a.Rw + (long long)b * a.rwstride : Rc;
+}
+
+// prior weight of trajectory b: the per-solve block when given, else the constants'.  Every
+// reader goes through this (gradient, costs, H and the component-pair flags of the envelope,
+// which must see the coupling of THIS trajectory's weight)
+__device__ __forceinline__ const double* big_pw(const BigArgs& a, const double* Pc, int b) {
+  return a.Pw ? a.Pw + (long long)b * a.pwstride : Pc;
 }
 
 // robust measurement rows (scalar rows): trajectory b's scales, or NULL = quadratic rows
@@ -343,7 +352,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_resid(BigArgs a, int final
   const double* Dt = (const double*)(a.cbuf + CL.Dt);
   const double* cw = (const double*)(a.cbuf + CL.cw);
   const double* Qw = (const double*)(a.cbuf + CL.Qw);
-  const double* Pw = (const double*)(a.cbuf + CL.Pw);
+  const double* Pw = big_pw(a, (const double*)(a.cbuf + CL.Pw), b);
   const double* Rw = big_rw(a, (const double*)(a.cbuf + CL.Rw), b);
   const double* md = nullptr;
   if constexpr (MHUBER) md = big_md(a, b);
@@ -721,7 +730,7 @@ __global__ __launch_bounds__(256, 4) void k_big_assemble(BigArgs a) {
   const double* D = (const double*)(a.cbuf + CL.D);
   const double* DCD = (const double*)(a.cbuf + CL.DCD);
   const double* Qw = (const double*)(a.cbuf + CL.Qw);
-  const double* Pw = (const double*)(a.cbuf + CL.Pw);
+  const double* Pw = big_pw(a, (const double*)(a.cbuf + CL.Pw), b);
   const double* PhiE = (const double*)(a.cbuf + CL.PhiE);
   const int E = a.M > 0 ? *(const int*)(a.cbuf + CL.ne) : 0;
   // wave-uniform work decomposition (SGPRs: the tile position, pair chunk and table reads are scalar)
@@ -2147,7 +2156,7 @@ __device__ double big_cost(const BigArgs& a, const double* X, int b, double* red
   const double* Dt = (const double*)(a.cbuf + CL.Dt);
   const double* cw = (const double*)(a.cbuf + CL.cw);
   const double* Qw = (const double*)(a.cbuf + CL.Qw);
-  const double* Pw = (const double*)(a.cbuf + CL.Pw);
+  const double* Pw = big_pw(a, (const double*)(a.cbuf + CL.Pw), b);
   const double* Rw = big_rw(a, (const double*)(a.cbuf + CL.Rw), b);
   const double* md = nullptr;
   if constexpr (MHUBER) md = big_md(a, b);

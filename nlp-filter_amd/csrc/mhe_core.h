@@ -188,7 +188,14 @@ struct GnArgs {
   double* cov;              // MODE_COV: (B, nq, n, n)
   const double* md;         // pseudo-Huber scale per measurement row (B|1, M) or NULL (mhe_solve_args.meas_delta):
   long long mdstride;       //   read by the MHUBER instances only
+  const double* Pw;         // per-solve prior weight (B|1, n, n) or NULL = the constants' Pw (mhe_solve_args.Pw);
+  long long pwstride;       //   build_tiles adds Pw_b - Pw_const to the node-0 block that Cc carries
 };
+
+// The prior weight of trajectory b: the per-solve block, or the constants' (a wave-uniform select)
+__device__ __forceinline__ const double* prior_weight(const GnArgs& a, const ConstLayout& CL, int b) {
+  return a.Pw ? a.Pw + (long long)b * a.pwstride : (const double*)(a.cbuf + CL.Pw);
+}
 
 #ifdef MHE_DIAG
 // Diagnostic build: s_memtime stamps at phase boundaries (wave 0), summed per
@@ -750,11 +757,11 @@ __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLa
 // Gradient g = J^T W r (nlp/nlp.py:242-286 objective); writes BV = -g (padding 0).
 //   g_j = a sum_k D_kj V_k - F_j^T V_j - sum_i Phi_ij GE_i (+ Pw (X_0 - x0) at j = 0)
 // TPR lanes per node: half sum the D column, half the Phi column.
-template <class DYN>
+// PW: the instance reads the per-solve prior weight a.Pw (prior_weight); false: the constants' only
+template <class DYN, bool PW = true>
 __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm, int b) {
   constexpr int n = DYN::n;
   const __amdgpu_buffer_rsrc_t rs = cbuf_rsrc(a.cbuf, CL.total);
-  const double* Pw = (const double*)(a.cbuf + CL.Pw);
   const double* Vs = sm + SL.Vs;
   const double* FtV = sm + SL.FtV;
   const double* GE = sm + SL.GE;
@@ -810,6 +817,7 @@ __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout&
 #pragma unroll
     for (int c = 0; c < n; ++c) gv[c] = a.alpha * s[c] - FtV[j * n + c] - o[c];
     if (a.has_prior && j == 0) {
+      const double* Pw = PW ? prior_weight(a, CL, b) : (const double*)(a.cbuf + CL.Pw);
       double r0[n];
 #pragma unroll
       for (int c = 0; c < n; ++c) r0[c] = Xs[c] - a.x0[(long long)b * n + c];
@@ -935,7 +943,7 @@ __device__ __forceinline__ void build_slots_n2(const GnArgs& a, const ConstLayou
 // BOUNDED (projected Newton, k_gn_bounded): rows and columns of the epsilon-active
 // unknowns (ACT) are replaced by their diagonal entries -- the reduced GN system on
 // the free unknowns, a diagonally scaled gradient step on the active ones.
-template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false>
+template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false, bool PW = true>
 __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
                                             d4 (&acc)[SLOTS], int wave, int lane, int stab) {
   const int* ACT = (const int*)(sm + SL.ACT);
@@ -1029,6 +1037,15 @@ __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& 
     if (s & 1) __builtin_amdgcn_sched_barrier(0);
   }
   double* DT = sm + SL.DT;
+  // per-solve prior weight (mhe_solve_args.Pw): Cc carries the constants' Pw in the node-0
+  // block -- inside diagonal tile 0 for n <= 16, the only sizes this path has pairs for (the
+  // entry points refuse Pw beyond) -- so that tile's owner adds Pw_b - Pw_const, before the
+  // active-set masking (exactly 0 when the two are equal: the tile is then bitwise the one
+  // without a per-solve weight)
+  const double* Pwb = nullptr;
+  const double* Pwc = (const double*)(a.cbuf + CL.Pw);
+  if constexpr (PW)
+    if (a.Pw) Pwb = prior_weight(a, CL, blockIdx.x);
   for (int J = wave; J < a.NT; J += NW) {
     const int ti = tile_index(J, J, a.NT);
     const size_t off = (size_t)ti * 256 + lane;
@@ -1050,6 +1067,12 @@ __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& 
         db = DB[off + 64 * r];
       }
       double v = h_element<DYN, MEAS, HUBER>(a, Phi, Es, FtE, G, Cc[off + 64 * r], da, db, 16 * J + tr, col, Dm, LAM);
+      if constexpr (PW) {
+        if (Pwb && 16 * J + tr < n && col < n) {
+          const int e = (16 * J + tr) * n + col;
+          v += Pwb[e] - Pwc[e];
+        }
+      }
       if (BOUNDED && (ACT[16 * J + tr] | ACT[col]) && 16 * J + tr != col) v = 0.0;
       DT[J * DTS + tr * 16 + (lane & 15)] = v;
     }
@@ -1999,8 +2022,11 @@ __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL,
 // anyway), which may use 256 VGPRs
 // SB: the small-batch factorization (factor_forward_sb, MODE_SOLVE with MINW = 2 only)
 // MHUBER: robust measurement rows (meas_row; a.md is read)
+// PW: a.Pw (the per-solve prior weight) is read, through a wave-uniform branch.  false: the
+// instance a plain MODE_SOLVE without Pw runs -- the parent's code (with the branch the C2
+// instance gained 12 B of scratch: profiles/arrival_resource_usage.txt)
 template <class DYN, class MEAS, int SLOTS, int mode, bool HUBER = false, int MINW = MHE_GN_MINW, bool SB = false,
-          bool MHUBER = false>
+          bool MHUBER = false, bool PW = true>
 __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   constexpr int n = DYN::n;
   static_assert(!SB || (mode == MODE_SOLVE && MINW <= 2 && NW == 8), "small-batch factorization: one workgroup per CU");
@@ -2059,7 +2085,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     DIAG_MARK(6);
     __syncthreads();
     DIAG_MARK(0);
-    c1 += grad_phase<DYN>(FA, FCL, FSL, sm, opaque_s(b));
+    c1 += grad_phase<DYN, PW>(FA, FCL, FSL, sm, opaque_s(b));
     {
       // park this wave's part of the cost in LDS (a live register across the
       // factorization would spill): read back if the loop exits at this iterate
@@ -2111,7 +2137,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       return;
     }
     if (it >= a.max_iter) break;
-    build_tiles<DYN, MEAS, SLOTS, HUBER>(FA, FCL, FSL, sm, acc, wave, lane, stab);
+    build_tiles<DYN, MEAS, SLOTS, HUBER, false, PW>(FA, FCL, FSL, sm, acc, wave, lane, stab);
     DIAG_MARK(15);
     __syncthreads();
     DIAG_MARK(2);
@@ -2152,7 +2178,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       // final cost at the converged iterate
       double cf = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER>(FA, FCL, FSL, sm, opaque_s(b));
       __syncthreads();
-      cf += grad_phase<DYN>(FA, FCL, FSL, sm, opaque_s(b));
+      cf += grad_phase<DYN, PW>(FA, FCL, FSL, sm, opaque_s(b));
       double z = 0.0;
       block_reduce2(RED, cf, z, false);
       if (threadIdx.x == 0) a.cost[b] = cf;
@@ -2326,7 +2352,7 @@ __global__ __launch_bounds__(NTHREADS, MHE_GN_MINW) void k_gn_bounded(GnArgs a) 
       nzt = 0.0;
       ct = node_meas_phase<DYN, MEAS, HUBER, true, MHUBER>(FA, FCL, FSLB, sm, opaque_s(b), &nzt);
       if (threadIdx.x == 0 && a.has_prior)
-        ct += prior_cost<n>(a, (const double*)(a.cbuf + FCL.Pw), Xs, b);
+        ct += prior_cost<n>(a, prior_weight(a, FCL, b), Xs, b);
       block_reduce2(RED, ct, pred, false);
       {
         double z = 0.0;
@@ -2662,9 +2688,13 @@ int launch_gn(const mhe_dims* dm, GnArgs& a, int batch, int mode, hipStream_t st
       }
     } else if (bounded) kern = huber ? k_gn_bounded<DYN, MEAS, MAX_SLOTS, true> : k_gn_bounded<DYN, MEAS, MAX_SLOTS>;
     else if (mode == MODE_SOLVE)
+      // the plain L2 solve keeps the instance without the per-solve prior weight (PW = false) for
+      // calls that pass none; every other instance reads a.Pw behind a branch
       kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE, true>
-             : sb  ? k_gn<DYN, MEAS, SB_SLOTS, MODE_SOLVE, false, 2, true>
-                   : k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE>;
+             : sb  ? (a.Pw ? k_gn<DYN, MEAS, SB_SLOTS, MODE_SOLVE, false, 2, true>
+                           : k_gn<DYN, MEAS, SB_SLOTS, MODE_SOLVE, false, 2, true, false, false>)
+                   : (a.Pw ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE>
+                           : k_gn<DYN, MEAS, MAX_SLOTS, MODE_SOLVE, false, MHE_GN_MINW, false, false, false>);
     else if (mode == MODE_ASSEMBLE)
       kern = huber ? k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE, true> : k_gn<DYN, MEAS, MAX_SLOTS, MODE_ASSEMBLE>;
     else if (mode == MODE_COV) {

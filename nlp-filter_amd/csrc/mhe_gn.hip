@@ -343,6 +343,14 @@ int check_row_args(const mhe_dims* dims, const double* Rw, const double* meas_de
   return MHE_OK;
 }
 
+// The per-solve prior weight of mhe_solve_args needs the addInitialCost term; on the register-
+// resident path its block must lie inside diagonal tile 0 (n <= 16: every pair that path has).
+int check_pw_arg(const mhe_dims* dims, const double* Pw) {
+  if (!Pw) return MHE_OK;
+  if (!dims->has_prior || (!is_big(dims) && dims->n > 16)) return MHE_ERR_UNSUPPORTED;
+  return MHE_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------ large-system parity I/O
@@ -489,6 +497,90 @@ __global__ void k_big_export_delta(BigArgs a, int batch, int ld, double* delta) 
   delta[e] = a.state[b] == BIG_RUNNING ? v : NAN;
 }
 
+// ------------------------------------------------------------ arrival cost (mhe_arrival)
+// After the covariance stage (k_gn<MODE_COV> / BIG_STAGE_COV, one query) has left the n x n
+// block C = S_t H^-1 S_t^T of every trajectory in `cov` and its outcome in `status`: one
+// wavefront per trajectory, the block in LDS (n <= ARR_NMAX),
+//   1. Cholesky C = L L^T, right-looking, with true sqrt and division (n is tiny and the
+//      result is the next window's weight: no reciprocal-square-root estimate here);
+//   2. L^-1 column by column (lane c: forward substitution of e_c), then A = L^-T L^-1,
+//      A_ij = sum_{k >= j} (L^-1)_ki (L^-1)_kj for i <= j in increasing k, written to both
+//      (i, j) and (j, i): bitwise symmetric;
+//   3. x(t) = sum_j phi_j X_j in node order.
+// A pivot that is not > 0 or not finite sets MHE_STATUS_NOT_SPD; wherever the status is
+// non-zero x_arr, Pw_arr and the covariance block are NaN.  `cov` may be Pw_arr itself (the
+// block is read into LDS before anything is written).  Sums are per trajectory and ordered:
+// the result does not depend on the batch.
+constexpr int ARR_NMAX = 40;
+__global__ __launch_bounds__(64) void k_arrival(int n, int P, int batch, const double* X, const double* phi,
+                                                double* cov, double* Pw_arr, double* x_arr, int* status) {
+  __shared__ double Ls[ARR_NMAX * ARR_NMAX];  // C, then L (lower triangle)
+  __shared__ double Ms[ARR_NMAX * ARR_NMAX];  // L^-1 (lower triangle)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= batch) return;
+  const int nn = n * n;
+  double* Cb = cov + (size_t)b * nn;
+  double* Ab = Pw_arr + (size_t)b * nn;
+  bool ok = status[b] == 0;  // wave-uniform
+  if (ok) {
+    for (int t = lane; t < nn; t += 64) {
+      const int i = t / n, j = t - i * n;
+      Ls[t] = Cb[i >= j ? t : j * n + i];  // the lower triangle, mirrored (the block is symmetric)
+      Ms[t] = 0.0;
+    }
+    __syncthreads();
+    for (int k = 0; k < n && ok; ++k) {
+      const double d = Ls[k * n + k];
+      if (!(d > 0.0) || !(d < INFINITY)) {
+        ok = false;
+        break;
+      }
+      const double lkk = sqrt(d);
+      __syncthreads();  // every lane has read the pivot
+      for (int i = k + lane; i < n; i += 64) Ls[i * n + k] = i == k ? lkk : Ls[i * n + k] / lkk;
+      __syncthreads();
+      const int mrem = n - k - 1;
+      for (int t = lane; t < mrem * mrem; t += 64) {
+        const int i = k + 1 + t / mrem, j = k + 1 + t % mrem;
+        if (j <= i) Ls[i * n + j] -= Ls[i * n + k] * Ls[j * n + k];
+      }
+      __syncthreads();
+    }
+  }
+  if (ok) {
+    for (int c = lane; c < n; c += 64) {  // column c of L^-1
+      Ms[c * n + c] = 1.0 / Ls[c * n + c];
+      for (int i = c + 1; i < n; ++i) {
+        double s = 0.0;
+        for (int k = c; k < i; ++k) s += Ls[i * n + k] * Ms[k * n + c];
+        Ms[i * n + c] = -s / Ls[i * n + i];
+      }
+    }
+    __syncthreads();
+    for (int t = lane; t < nn; t += 64) {
+      const int i = t / n, j = t - i * n;
+      if (i <= j) {
+        double s = 0.0;
+        for (int k = j; k < n; ++k) s += Ms[k * n + i] * Ms[k * n + j];
+        Ab[i * n + j] = s;
+        Ab[j * n + i] = s;
+      }
+    }
+    for (int c = lane; c < n; c += 64) {
+      double s = 0.0;
+      for (int j = 0; j < P; ++j) s += phi[j] * X[((size_t)b * P + j) * n + c];
+      x_arr[(size_t)b * n + c] = s;
+    }
+  } else {
+    for (int t = lane; t < nn; t += 64) {
+      Ab[t] = NAN;
+      Cb[t] = NAN;
+    }
+    for (int c = lane; c < n; c += 64) x_arr[(size_t)b * n + c] = NAN;
+    if (lane == 0 && status[b] == 0) status[b] = MHE_STATUS_NOT_SPD;
+  }
+}
+
 }  // namespace mhe
 
 #ifdef MHE_DIAG
@@ -578,7 +670,7 @@ int mhe_gn_solve_ext(const mhe_dims* dims, const void* const_buf, int32_t batch,
   g.Y = Y; g.PAR = PAR; g.par_bstride = par_bstride; g.Rw = nullptr; g.rw_bstride = 0; g.x0 = x0;
   g.cost_out = cost_out; g.iters_out = iters_out; g.status_out = status_out; g.max_iter = max_iter; g.tol = tol;
   g.workspace = workspace; g.workspace_bytes = workspace_bytes;
-  g.meas_delta = nullptr; g.md_bstride = 0;
+  g.meas_delta = nullptr; g.md_bstride = 0; g.Pw = nullptr; g.pw_bstride = 0;
   return mhe_solve(dims, const_buf, &g, stream);
 }
 
@@ -596,6 +688,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
       (dims->n_extra > 0 && (!g->Z0 || !g->Z_out)))
     return MHE_ERR_NULL;
   rc = check_row_args(dims, g->Rw, g->meas_delta);  // per-solve weights / robust rows
+  if (rc == MHE_OK) rc = check_pw_arg(dims, g->Pw);
   if (rc != MHE_OK) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
@@ -605,6 +698,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
     BigArgs A = make_big_args(dims, const_buf, NT, g->workspace);
     A.U = g->U; A.ustride = g->u_bstride; A.Y = g->Y; A.PAR = g->PAR; A.pstride = g->par_bstride; A.x0 = g->x0;
     A.Rw = g->Rw; A.rwstride = g->rw_bstride; A.md = g->meas_delta; A.mdstride = g->md_bstride;
+    A.Pw = g->Pw; A.pwstride = g->pw_bstride;
     A.X = g->X_out; A.cost = g->cost_out; A.iters = g->iters_out; A.state = g->status_out; A.tol = g->tol;
     A.Z = g->Z_out;
     A.lam = dims->n_eq > 0 ? g->lambda_out : nullptr;
@@ -624,7 +718,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   a.X0 = g->X0; a.Xout = g->X_out; a.U = g->U; a.ustride = g->u_bstride; a.Y = g->Y; a.PAR = g->PAR;
   a.pstride = g->par_bstride; a.x0 = g->x0; a.cost = g->cost_out; a.iters = g->iters_out; a.status = g->status_out;
   a.max_iter = g->max_iter; a.tol = g->tol; a.Rw = g->Rw; a.rwstride = g->rw_bstride;
-  a.md = g->meas_delta; a.mdstride = g->md_bstride;
+  a.md = g->meas_delta; a.mdstride = g->md_bstride; a.Pw = g->Pw; a.pwstride = g->pw_bstride;
   return ops->gn(dims, a, batch, MODE_SOLVE, st);
 }
 
@@ -658,6 +752,7 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
       (dims->has_prior && !at->x0))
     return MHE_ERR_NULL;
   rc = check_row_args(dims, at->Rw, at->meas_delta);  // as mhe_solve
+  if (rc == MHE_OK) rc = check_pw_arg(dims, at->Pw);
   if (rc != MHE_OK) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
@@ -669,6 +764,7 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
     A.n_bounds = 0;  // the unconstrained GN model at X (bounds are not reflected)
     A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
     A.Rw = at->Rw; A.rwstride = at->rw_bstride; A.md = at->meas_delta; A.mdstride = at->md_bstride;
+    A.Pw = at->Pw; A.pwstride = at->pw_bstride;
     A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
     A.cost = (double*)scratch; A.state = status_out;
     A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
@@ -682,9 +778,36 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
   GnArgs a = make_args(dims, const_buf, NT);
   a.X0 = at->X0; a.U = at->U; a.ustride = at->u_bstride; a.Y = at->Y; a.PAR = at->PAR; a.pstride = at->par_bstride;
   a.x0 = at->x0; a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.md = at->meas_delta; a.mdstride = at->md_bstride;
+  a.Pw = at->Pw; a.pwstride = at->pw_bstride;
   a.status = status_out;
   a.PhiQ = PhiQ; a.nq = n_query; a.cov = cov_out;
   return ops->gn(dims, a, batch, MODE_COV, st);
+}
+
+size_t mhe_arrival_scratch_bytes(const mhe_dims* dims, int32_t batch) { return mhe_cov_scratch_bytes(dims, batch, 1); }
+
+int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
+                double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
+                size_t scratch_bytes, void* stream) {
+  int NT = 0;
+  int rc = check_dims(dims, &NT);
+  if (rc != MHE_OK) return rc;
+  if (dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED || dims->n > ARR_NMAX)
+    return MHE_ERR_UNSUPPORTED;
+  if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_state_cov: one 16-column panel
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  if (at->batch < 0) return MHE_ERR_DIMS;
+  if (!phi || !x_arr || !Pw_arr || !status_out) return MHE_ERR_NULL;
+  if (at->batch == 0) return MHE_OK;
+  // the covariance stage of mhe_state_cov, one query: the block into cov_out when the caller
+  // wants it, else into Pw_arr, which k_arrival then inverts in place
+  double* cov = cov_out ? cov_out : Pw_arr;
+  rc = mhe_state_cov(dims, const_buf, at, phi, 1, cov, status_out, scratch, scratch_bytes, stream);
+  if (rc != MHE_OK) return rc;
+  hipLaunchKernelGGL(k_arrival, dim3(at->batch), dim3(64), 0, (hipStream_t)stream, dims->n, dims->N + 1, at->batch,
+                     at->X0, phi, cov, Pw_arr, x_arr, status_out);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
 int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
@@ -715,8 +838,8 @@ int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const
 // mhe_assemble with the per-solve row inputs (mhe_assemble_at); the positional call passes none
 static int assemble_reg(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
                         int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
-                        const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride, double* H,
-                        double* g, double* cost, void* stream) {
+                        const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride,
+                        const double* Pw, int64_t pw_bstride, double* H, double* g, double* cost, void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
@@ -730,15 +853,15 @@ static int assemble_reg(const mhe_dims* dims, const void* const_buf, int32_t bat
   GnArgs a = make_args(dims, const_buf, NT);
   a.X0 = X; a.U = U; a.ustride = u_bstride; a.Y = Y; a.PAR = PAR; a.pstride = par_bstride; a.x0 = x0;
   a.Hout = H; a.gout = g; a.cost = cost;
-  a.Rw = Rw; a.rwstride = rw_bstride; a.md = md; a.mdstride = md_bstride;
+  a.Rw = Rw; a.rwstride = rw_bstride; a.md = md; a.mdstride = md_bstride; a.Pw = Pw; a.pwstride = pw_bstride;
   return ops->gn(dims, a, batch, MODE_ASSEMBLE, (hipStream_t)stream);
 }
 
 int mhe_assemble(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
                  int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
                  double* H, double* g, double* cost, void* stream) {
-  return assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0, H, g,
-                      cost, stream);
+  return assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0,
+                      nullptr, 0, H, g, cost, stream);
 }
 
 int mhe_chol_solve(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,
@@ -814,17 +937,18 @@ int32_t mhe_kkt_dim(const mhe_dims* dims) {
 static int assemble_kkt(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
                         const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
                         const double* x0, const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride,
-                        double* H, double* g, double* cost, int32_t* status, void* workspace, size_t workspace_bytes,
-                        void* stream) {
+                        const double* Pw, int64_t pw_bstride, double* H, double* g, double* cost, int32_t* status,
+                        void* workspace, size_t workspace_bytes, void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
   rc = check_row_args(dims, Rw, md);
+  if (rc == MHE_OK) rc = check_pw_arg(dims, Pw);
   if (rc != MHE_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!is_big(dims)) {
     rc = assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, Rw, rw_bstride, md, md_bstride,
-                      H, g, cost, stream);
+                      Pw, pw_bstride, H, g, cost, stream);
     if (rc == MHE_OK && status && batch > 0 && hipMemsetAsync(status, 0, sizeof(int32_t) * batch, st) != hipSuccess)
       return MHE_ERR_HIP;
     return rc;
@@ -839,7 +963,7 @@ static int assemble_kkt(const mhe_dims* dims, const void* const_buf, int32_t bat
   BigArgs A = make_big_args(dims, const_buf, NT, workspace);
   A.n_bounds = 0;  // the plain GN system: the projected method's reduction belongs to the solve
   A.U = U; A.ustride = u_bstride; A.Y = Y; A.PAR = PAR; A.pstride = par_bstride; A.x0 = x0;
-  A.Rw = Rw; A.rwstride = rw_bstride; A.md = md; A.mdstride = md_bstride;
+  A.Rw = Rw; A.rwstride = rw_bstride; A.md = md; A.mdstride = md_bstride; A.Pw = Pw; A.pwstride = pw_bstride;
   A.X = const_cast<double*>(X);  // read only by k_big_resid / k_big_assemble
   A.Z = const_cast<double*>(Z);  // read only by k_big_resid
   A.cost = cost; A.state = status;
@@ -861,8 +985,8 @@ int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t bat
                         const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
                         const double* x0, double* H, double* g, double* cost, int32_t* status, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  return assemble_kkt(dims, const_buf, batch, X, Z, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0, H, g,
-                      cost, status, workspace, workspace_bytes, stream);
+  return assemble_kkt(dims, const_buf, batch, X, Z, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0,
+                      nullptr, 0, H, g, cost, status, workspace, workspace_bytes, stream);
 }
 
 int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, double* H, double* g,
@@ -873,8 +997,8 @@ int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve
   if (!at) return MHE_ERR_NULL;
   if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
   return assemble_kkt(dims, const_buf, at->batch, at->X0, at->Z0, at->U, at->u_bstride, at->Y, at->PAR,
-                      at->par_bstride, at->x0, at->Rw, at->rw_bstride, at->meas_delta, at->md_bstride, H, g, cost,
-                      status, at->workspace, at->workspace_bytes, stream);
+                      at->par_bstride, at->x0, at->Rw, at->rw_bstride, at->meas_delta, at->md_bstride, at->Pw,
+                      at->pw_bstride, H, g, cost, status, at->workspace, at->workspace_bytes, stream);
 }
 
 int mhe_chol_solve_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,

@@ -54,7 +54,7 @@ class MheLsDims(_Sized):
 class MheSolveArgs(_Sized):
     _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("X0", c_vp), ("X_out", c_vp), ("Z0", c_vp), ("Z_out", c_vp),
                 ("U", c_vp), ("u_bstride", c_i64), ("Y", c_vp), ("PAR", c_vp), ("par_bstride", c_i64),
-                ("Rw", c_vp), ("rw_bstride", c_i64), ("x0", c_vp), ("cost_out", c_vp), ("iters_out", c_vp),
+                ("Rw", c_vp), ("rw_bstride", c_i64), ("Pw", c_vp), ("pw_bstride", c_i64), ("x0", c_vp), ("cost_out", c_vp), ("iters_out", c_vp),
                 ("status_out", c_vp), ("max_iter", c_i32), ("tol", c_dbl), ("workspace", c_vp),
                 ("workspace_bytes", c_sz), ("lambda_out", c_vp), ("meas_delta", c_vp), ("md_bstride", c_i64)]
 
@@ -93,6 +93,9 @@ SIGNATURES = {
     "mhe_cov_scratch_bytes": (c_sz, [_P, c_i32, c_i32]),
     "mhe_state_cov": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
                                      c_vp]),
+    "mhe_arrival_scratch_bytes": (c_sz, [_P, c_i32]),
+    "mhe_arrival": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                   c_vp]),
     "mhe_ekf_run": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -319,10 +319,38 @@ class BatchSolver:
             raise ValueError("meas_delta must be > 0 (+inf = quadratic row)")
         return t, (0 if t.shape[0] == 1 else self.M)
 
+    def _pw(self, Pw, B):
+        """Per-solve prior weight (mhe_solve_args.Pw): (B|1, n, n) or (n, n), float64, every
+        block symmetric (checked exactly; the blocks mhe_arrival writes are, NaN blocks of a
+        failed trajectory pass and keep that trajectory NaN); needs a prior.  None = the
+        weight the constants were built with."""
+        if Pw is None:
+            return None, 0
+        if not self.dims.has_prior:
+            raise ValueError("per-solve Pw needs a prior (construct the solver with Pw, e.g. zeros)")
+        if isinstance(Pw, torch.Tensor):
+            if Pw.dtype != torch.float64:
+                raise ValueError(f"Pw must be float64, got {Pw.dtype}")
+        else:
+            Pw = np.asarray(Pw)
+            if Pw.dtype != np.float64:
+                raise ValueError(f"Pw must be float64, got {Pw.dtype}")
+        n = self.n
+        t = _dev(Pw, self.device)
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() != 3 or t.shape[1:] != (n, n) or t.shape[0] not in (1, B):
+            raise ValueError(f"Pw must be (B|1, {n}, {n}) or ({n}, {n}), got {tuple(t.shape)}")
+        tt = t.transpose(1, 2)
+        if not bool(((t == tt) | ((t != t) & (tt != tt))).all()):
+            raise ValueError("Pw must be symmetric (every (n, n) block equal to its transpose)")
+        return t, (0 if t.shape[0] == 1 else n * n)
+
     def _gn(self, s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
-            Z=None, Zo=None, Rw=None, lam=None, meas_delta=None):
+            Z=None, Zo=None, Rw=None, lam=None, meas_delta=None, Pw=None):
         Rw_t, rstr = self._rw(Rw, B)
         md_t, mstr = self._md(meas_delta, B)
+        Pw_t, wstr = self._pw(Pw, B)
         if B == 0:
             return
         chunk = self._chunk(B, s)
@@ -353,15 +381,19 @@ class BatchSolver:
             a.workspace, a.workspace_bytes = (None if ws is None else ctypes.c_void_p(ws.data_ptr())), nb
             a.lambda_out = at(lam, self.n_eq)
             a.meas_delta, a.md_bstride = at(md_t, 0, mstr), mstr
+            a.Pw, a.pw_bstride = at(Pw_t, 0, wstr), wstr
             rc = self.lib.mhe_solve(self.dims, _ptr(self.cbuf), ctypes.byref(a), _handle(s))
             _lib.check(rc, "mhe_solve")
-        keep_alive(s, cur, X, Xo, Z, Zo, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, cost, iters, status, ws, lam)
+        keep_alive(s, cur, X, Xo, Z, Zo, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, cost, iters, status, ws, lam)
 
     # ------------------------------------------------------------------ calls
     def solve(self, X0, U, Y, PAR=None, x0=None, max_iter=20, tol=1e-10, stream=None, out=None, Z0=None, Rw=None,
-              lam_out=None, meas_delta=None):
+              lam_out=None, meas_delta=None, Pw=None):
         """Gauss-Newton to convergence. Returns (X, cost, iters, status) device tensors,
         and the extra variables Z (B, n_extra) as a fifth element when n_extra > 0.
+        ``Pw`` (B|1, n, n) or (n, n), float64, symmetric: the prior (arrival-cost) weight of
+        this solve per trajectory, replacing the constants' (every model and solve mode; needs
+        a prior) -- ``arrival()`` returns the next window's as a device tensor.
         ``Rw`` (B|1, M, p, p) -- (B|1, M) for mixed rows -- replaces the measurement
         weights of the constants for this solve (nonlinear models; the MHE windows'
         R = 0 slot masks).  ``meas_delta`` (B|1, M) or (M,), float64, > 0: the pseudo-Huber
@@ -396,7 +428,7 @@ class BatchSolver:
                 else:
                     lam = torch.zeros((B, self.n_eq), dtype=torch.float64, device=self.device)
             self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol, Z, Zo,
-                     Rw, lam, meas_delta)
+                     Rw, lam, meas_delta, Pw)
             self.lam = lam
         if self.n_extra:
             return Xo, cost, iters, status, Zo
@@ -406,13 +438,13 @@ class BatchSolver:
         """Pre-stage device inputs once (bench: inputs resident before timing)."""
         return self._inputs(X0, U, Y, PAR, x0)
 
-    def solve_staged(self, staged, outs, max_iter, tol, stream=None, meas_delta=None):
+    def solve_staged(self, staged, outs, max_iter, tol, stream=None, meas_delta=None, Pw=None):
         X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = staged
         Xo, cost, iters, status = outs
         self._check_ready()
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
             self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
-                     meas_delta=meas_delta)
+                     meas_delta=meas_delta, Pw=Pw)
 
     def resjac(self, X, U, Y, PAR=None, stream=None):
         """Per-node defects W (B,P,n) and dynamics Jacobians F (B,P,n,n), per-row
@@ -438,13 +470,14 @@ class BatchSolver:
         border rows for a bordered (KKT) problem (mhe_kkt_dim)."""
         return self.lib.mhe_kkt_dim(self.dims)
 
-    def assemble(self, X, U, Y, PAR=None, x0=None, stream=None, status_out=False, Z=None, Rw=None, meas_delta=None):
+    def assemble(self, X, U, Y, PAR=None, x0=None, stream=None, status_out=False, Z=None, Rw=None, meas_delta=None,
+                 Pw=None):
         """GN normal equations at X: H (B,dp,dp), g (B,dp), cost (B) -- dense, node-major
         (row j*n + c; padding nodes last) on both paths.  The large-system path runs the
         solve's own k_big_resid + k_big_assemble over a workspace (mhe_assemble_kkt_ws) and
         copies H out of their component-major tiles.  A bordered problem (n_extra / n_eq
         > 0) returns the KKT system of kkt_dim rows instead (H_xz, H_zz, the constraint
-        rows; g = [g_x; g_z; C v - r]) at (X, Z).  ``Rw`` / ``meas_delta`` as for solve():
+        rows; g = [g_x; g_z; C v - r]) at (X, Z).  ``Rw`` / ``meas_delta`` / ``Pw`` as for solve():
         the system a solve with them forms at X (mhe_assemble_at; with ``meas_delta`` the IRLS
         weights at X and the robust cost).  ``status_out``: also return the
         per-trajectory status (0, or 4 = constants built for other dims)."""
@@ -466,9 +499,10 @@ class BatchSolver:
             P, n, M = self.P, self.n, self.M
             Rw_t, rstr = self._rw(Rw, B)
             md_t, mstr = self._md(meas_delta, B)
+            Pw_t, wstr = self._pw(Pw, B)
             for lo in range(0, B, chunk):
                 c = min(chunk, B - lo)
-                if Rw_t is not None or md_t is not None:
+                if Rw_t is not None or md_t is not None or Pw_t is not None:
                     a = _lib.MheSolveArgs()
                     a.batch = c
                     a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, self.n_extra)
@@ -477,6 +511,7 @@ class BatchSolver:
                     a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
                     a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
                     a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
+                    a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
                     a.x0 = _at(x0_t, lo, n)
                     a.workspace, a.workspace_bytes = _ptr(ws), nb
                     rc = self.lib.mhe_assemble_at(self.dims, _ptr(self.cbuf), ctypes.byref(a), _at(H, lo, dk * dk),
@@ -488,12 +523,76 @@ class BatchSolver:
                     ustr, _at(Y_t, lo, M * self.p), _at(PAR_t, lo, pstr), pstr, _at(x0_t, lo, n), _at(H, lo, dk * dk),
                     _at(g, lo, dk), _at(cost, lo, 1), _at(status, lo, 1, 4), _ptr(ws), nb, _handle(s))
                 _lib.check(rc, "mhe_assemble_kkt_ws")
-            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, H, g, cost, status, ws)
+            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, H, g, cost, status, ws)
         if status_out:
             return H, g, cost, status
         return H, g, cost
 
-    def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None, meas_delta=None):
+    def _query_rows(self, t, Phi):
+        """Lagrange basis rows (Tq, P) at the query times ``t``, or the rows ``Phi`` as given."""
+        if (t is None) == (Phi is None):
+            raise ValueError("give the query times t or the basis rows Phi (one of them)")
+        if Phi is None:
+            from nlp.collocation import ChebyshevPseudospectralMethod
+            Phi = ChebyshevPseudospectralMethod(self.N, 0, self.T).lagrange_matrix(
+                np.asarray(t, dtype=np.float64).reshape(-1))
+        return np.asarray(Phi.cpu() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64).reshape(-1, self.P)
+
+    def arrival(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, meas_delta=None, Pw=None, stream=None,
+                with_cov=False):
+        """Arrival cost of the window shifted to the query time (mhe_arrival): with the
+        covariance block C = S_t H^-1 S_t^T of ``covariance()`` at X (same inputs, the window's
+        own ``Pw`` included), x_arr (B, n) = x(t) by the Lagrange row in node order and
+        Pw_arr (B, n, n) = inv(C), bitwise symmetric, formed on the device.  Exactly one query:
+        ``t`` a scalar (or one-element array) in [0, T], or its basis row ``Phi`` (1, P).
+        Returns (x_arr, Pw_arr, status) device tensors -- the next ``solve(x0=x_arr, Pw=Pw_arr)``
+        needs no copy -- and C (B, n, n) as a fourth element with ``with_cov`` (bitwise
+        ``covariance(..., t=[t])[0][:, 0]``).  status (B,): 0, 2 = not SPD (H or the block), 4 =
+        bad constants; the outputs of such a trajectory are NaN, the others unaffected.
+        Refusals as ``covariance()``."""
+        self._check_ready()
+        Phi = self._query_rows(t, Phi)
+        if Phi.shape[0] != 1:
+            raise ValueError(f"arrival() takes exactly one query time, got {Phi.shape[0]}")
+        with launch_stream(stream, self.device, (self._built,)) as (s, cur):
+            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
+            Rw_t, rstr = self._rw(Rw, B)
+            md_t, mstr = self._md(meas_delta, B)
+            Pw_t, wstr = self._pw(Pw, B)
+            phi = _dev(Phi, self.device)
+            n, P, M = self.n, self.P, self.M
+            f64 = dict(dtype=torch.float64, device=self.device)
+            x_arr = torch.empty((B, n), **f64)
+            Pw_arr = torch.empty((B, n, n), **f64)
+            cov = torch.empty((B, n, n), **f64) if with_cov else None
+            status = torch.empty(B, dtype=torch.int32, device=self.device)
+            chunk = max(1, self._chunk(B, s))  # streamed in chunks like covariance()
+            ws, nb = self._workspace(chunk, s)
+            sb = self.lib.mhe_arrival_scratch_bytes(self.dims, chunk)
+            scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
+            for lo in range(0, B, chunk):
+                a = _lib.MheSolveArgs()
+                a.batch = min(chunk, B - lo)
+                a.X0 = _at(X, lo, P * n)
+                a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
+                a.Y = _at(Y_t, lo, M * self.p)
+                a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
+                a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
+                a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
+                a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
+                a.x0 = _at(x0_t, lo, n)
+                a.workspace, a.workspace_bytes = _ptr(ws), nb
+                rc = self.lib.mhe_arrival(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(phi), _at(x_arr, lo, n),
+                                          _at(Pw_arr, lo, n * n), _at(cov, lo, n * n), _at(status, lo, 1, 4),
+                                          _ptr(scratch), sb, _handle(s))
+                _lib.check(rc, "mhe_arrival")
+            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, phi, x_arr, Pw_arr, cov, status, ws, scratch)
+        if with_cov:
+            return x_arr, Pw_arr, status, cov
+        return x_arr, Pw_arr, status
+
+    def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None, meas_delta=None,
+                   Pw=None):
         """Posterior covariance of the state at query times (mhe_state_cov): with H = J^T W J
         at X (the solve's own assembly: Huber weights, per-solve ``Rw``, the IRLS weights of
         ``meas_delta`` at X) and S_t = phi(t)^T (x)
@@ -503,15 +602,10 @@ class BatchSolver:
         (cov (B, Tq, n, n), status (B,): 0, 2 = not SPD, 4 = bad constants; cov is NaN where
         status != 0).  The inverse of the half-Hessian: a covariance when the weights are
         inverse covariances.  Bounds are not reflected; bordered and mixed-row problems are
-        refused (MHE_ERR_UNSUPPORTED)."""
+        refused (MHE_ERR_UNSUPPORTED).  ``Pw``: the per-solve prior weight, as for solve();
+        ``arrival()`` returns the inverse of one query's block without a host round trip."""
         self._check_ready()
-        if (t is None) == (Phi is None):
-            raise ValueError("give the query times t or the basis rows Phi (one of them)")
-        if Phi is None:
-            from nlp.collocation import ChebyshevPseudospectralMethod
-            Phi = ChebyshevPseudospectralMethod(self.N, 0, self.T).lagrange_matrix(
-                np.asarray(t, dtype=np.float64).reshape(-1))
-        Phi = np.asarray(Phi.cpu() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64).reshape(-1, self.P)
+        Phi = self._query_rows(t, Phi)
         Tq = Phi.shape[0]
         if Tq == 0:
             raise ValueError("at least one query time")
@@ -519,6 +613,7 @@ class BatchSolver:
             X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
             Rw_t, rstr = self._rw(Rw, B)
             md_t, mstr = self._md(meas_delta, B)
+            Pw_t, wstr = self._pw(Pw, B)
             PhiQ = _dev(Phi, self.device)
             n, P, M = self.n, self.P, self.M
             cov = torch.empty((B, Tq, n, n), dtype=torch.float64, device=self.device)
@@ -538,13 +633,14 @@ class BatchSolver:
                 a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
                 a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
                 a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
+                a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
                 a.x0 = _at(x0_t, lo, n)
                 a.workspace, a.workspace_bytes = _ptr(ws), nb
                 rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
                                             _at(cov, lo, Tq * n * n), _at(status, lo, 1, 4), _ptr(scratch), sb,
                                             _handle(s))
                 _lib.check(rc, "mhe_state_cov")
-            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, x0_t, PhiQ, cov, status, ws, scratch)
+            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, PhiQ, cov, status, ws, scratch)
         return cov, status
 
     def chol_solve(self, H, g, stream=None):

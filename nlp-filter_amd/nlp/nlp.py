@@ -593,6 +593,16 @@ class fixedTimeOptimalEstimationNLP(NLP):
         dname = _fname(func)
         dyn_par = registry.dyn_params(dname, self._dyn[1]) if dname in registry.DYN else None
         Pw = None if self._prior is None else np.asarray(_resolve(self._prior[0]), dtype=np.float64)
+        # A Parameter-valued prior weight (the arrival cost a moving horizon re-sets every
+        # window) travels per solve (mhe_solve_args.Pw), like a nonlinear model's R: the
+        # engine is built once, with a zero prior weight, and never rebuilt for it.  An
+        # ndarray weight stays part of the device constants.
+        Pw_solve = None
+        if Pw is not None and isinstance(self._prior[0], Param):
+            Pw_solve = Pw.reshape(self.n, self.n)
+            if not np.array_equal(Pw_solve, Pw_solve.T):
+                raise ValueError("the prior weight Q of addInitialCost must be symmetric")
+            Pw = np.zeros((self.n, self.n))
         bounds = self._enforced_bounds()
         if self._ineq or self._eq:
             bounds = []   # held by the active set as constraint rows (_ineq_rows)
@@ -627,6 +637,7 @@ class fixedTimeOptimalEstimationNLP(NLP):
             self._engine_key = key
             self.engine_builds = getattr(self, "engine_builds", 0) + 1
         self._Rw_solve = None if linear else Rw
+        self._Pw_solve = Pw_solve
         self._md_solve = dl if np.any(np.isfinite(dl)) else None  # per-row pseudo-Huber scales (per solve)
         self._PAR = PAR
         self._extra = extra
@@ -746,10 +757,12 @@ class fixedTimeOptimalEstimationNLP(NLP):
         if eng.n_eq:
             lam_t = torch.empty((1, eng.n_eq), dtype=torch.float64, device=eng.device)
         md = None if self._md_solve is None else self._md_solve[None]
+        Pw = None if self._Pw_solve is None else self._Pw_solve[None]
         out = eng.solve(X0, U, Y, PAR, x0, max_iter=self.max_iter, tol=self.tol, Z0=Z0, Rw=Rw, lam_out=lam_t,
-                        meas_delta=md)
+                        meas_delta=md, Pw=Pw)
         X, cost, iters, status = out[:4]
-        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, md=md, engine=eng)  # extractCovariance
+        # extractCovariance / extractArrivalCost
+        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, md=md, Pw=Pw, engine=eng)
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         X = X.cpu().numpy()[0]
@@ -781,30 +794,58 @@ class fixedTimeOptimalEstimationNLP(NLP):
         the solution, with that solve's controls, measurements, prior, R and -- for
         pseudo-Huber measurement rows -- their IRLS weights at the solution
         (BatchSolver.covariance).  A covariance when Q, R and the prior weight are inverse
-        covariances; e.g. ``inv(extractCovariance("x", [DT])[0])`` is the arrival-cost weight
-        of the next window.  State bounds are not reflected.  Raises UnsupportedFeature for
+        covariances; the arrival cost of the next window (its inverse at the shift time,
+        formed on the device) is ``extractArrivalCost``.  State bounds are not reflected.
+        Raises UnsupportedFeature for
         problems with mixed rows / extra variables, constraints (a covariance under
         constraints is a projected quantity), for a variable other than the state
         trajectory, and before the first solve()."""
-        last = getattr(self, "_last_solve", None)
-        if self.sol is None or last is None:
-            raise UnsupportedFeature("extractCovariance needs a solve() first")
-        if self._X is None or name != self._X[0].name:
-            raise UnsupportedFeature(f"extractCovariance: {name!r} is not the state trajectory")
-        eng = last["engine"]  # the engine of that solve (a re-set R or prior may have built another since)
-        if self._ineq or self._eq or self._active or eng.n_eq or eng.n_extra or eng.meas_name == "mixed":
-            raise UnsupportedFeature("extractCovariance: general (mixed-row), active-set and bordered problems "
-                                     "have no unconstrained covariance")
+        eng, last = self._cov_engine(name, "extractCovariance")
         import torch
         X = np.stack([x.value for x in self._X])[None]
         Phi = self.CPM.lagrange_matrix(np.asarray(t_array, dtype=np.float64).reshape(-1))
         cov, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"],
-                                     meas_delta=last["md"])
+                                     meas_delta=last["md"], Pw=last["Pw"])
         torch.cuda.synchronize()
         st = int(status.cpu().numpy()[0])
         if st != 0:
             warnings.warn(f"extractCovariance: the normal matrix at the solution is not usable (status {st})")
         return cov.cpu().numpy()[0]
+
+    def _cov_engine(self, name, what):
+        """The last solve's engine and inputs, or the refusals extractCovariance and
+        extractArrivalCost share."""
+        last = getattr(self, "_last_solve", None)
+        if self.sol is None or last is None:
+            raise UnsupportedFeature(f"{what} needs a solve() first")
+        if self._X is None or name != self._X[0].name:
+            raise UnsupportedFeature(f"{what}: {name!r} is not the state trajectory")
+        eng = last["engine"]  # the engine of that solve (a re-set R or prior may have built another since)
+        if self._ineq or self._eq or self._active or eng.n_eq or eng.n_extra or eng.meas_name == "mixed":
+            raise UnsupportedFeature(f"{what}: general (mixed-row), active-set and bordered problems "
+                                     "have no unconstrained covariance")
+        return eng, last
+
+    def extractArrivalCost(self, name, t):
+        """The next window's prior from the last solve, for a horizon shifted by ``t``:
+        (xhat (n,), Pw (n, n)) with xhat = x(t), what ``extractSolution(name, [t])[0]`` returns,
+        and Pw = inv(extractCovariance(name, [t])[0]), bitwise symmetric -- both formed on the
+        device (BatchSolver.arrival).  Feed them to setParameter: a Parameter-valued ``"Q"`` of
+        addInitialCost travels per solve, so the engine is not rebuilt.  Refusals as
+        extractCovariance."""
+        eng, last = self._cov_engine(name, "extractArrivalCost")
+        import torch
+        X = np.stack([x.value for x in self._X])[None]
+        Phi = self.CPM.lagrange_matrix(np.asarray(t, dtype=np.float64).reshape(-1))
+        if Phi.shape[0] != 1:
+            raise ValueError("extractArrivalCost takes one time")
+        x_arr, Pw_arr, status = eng.arrival(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"],
+                                            meas_delta=last["md"], Pw=last["Pw"])
+        torch.cuda.synchronize()
+        st = int(status.cpu().numpy()[0])
+        if st != 0:
+            warnings.warn(f"extractArrivalCost: the covariance at the solution is not usable (status {st})")
+        return x_arr.cpu().numpy()[0], Pw_arr.cpu().numpy()[0]
 
     def _check_bounds(self):
         viol = False

@@ -111,7 +111,7 @@ extern "C" {
  * the size queries) unless it equals this build's sizeof -- a binding that
  * declares an older or truncated struct is refused before any later field is
  * read.  (mhe/_lib.py sets it in the ctypes constructors.) */
-#define MHE_ABI_VERSION 10
+#define MHE_ABI_VERSION 11
 
 typedef struct mhe_dims {
   int32_t struct_size;  /* = sizeof(mhe_dims)                                */
@@ -535,6 +535,46 @@ size_t mhe_arrival_scratch_bytes(const mhe_dims* dims, int32_t batch);
 int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
                 double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
                 size_t scratch_bytes, void* stream);
+
+/* Covariance and arrival cost of mixed-row and bordered problems (ABI v11): what
+ * mhe_state_cov and mhe_arrival refuse -- MHE_MEAS_MIXED rows, extra variables z
+ * (n_extra > 0) and equality rows C v = r (n_eq > 0).  The covariance of the estimate under
+ * its equality rows is the leading block of the inverse of the bordered system every GN step
+ * of such a problem solves (mhe_assemble_kkt_ws:  [H Bd; Bd^T G], Bd = [H_xz C^T],
+ * G = diag(H_zz, 0), K = n_extra + n_eq border columns).  With H = L L^T (the solve's
+ * factorization, pivots refined as for mhe_state_cov), Z_q = L^-1 S_q^T, V = L^-1 Bd,
+ * Sigma = G - V^T V (the Schur matrix of the bordered step, factored as L D L^T without
+ * pivoting as there) and T_q = V^T Z_q,
+ *   Cov[x(t_q)] = Z_q^T Z_q + T_q^T Sigma^-1 T_q         cov_out  (B, n_query, n, n)
+ *   Cov[z]      = (Sigma^-1)[0:n_extra, 0:n_extra]        covz_out (B, n_extra, n_extra) or NULL
+ * each block written from its upper triangle (bitwise symmetric).  Equality rows take
+ * variance away: the blocks are positive SEMI-definite (a row x_a - x_b = r leaves the
+ * variance of x_a - x_b at 0).  An extra variable no row depends on is held by the solve
+ * (zero Schur pivot) and removed here: its row and column of covz_out are NaN, every other
+ * entry is that of the system without it.  eq_rhs does not enter; bounds are not reflected.
+ *
+ *   at          as for mhe_state_cov, plus Z0 (B, n_extra), required when n_extra > 0
+ *               (MHE_ERR_NULL); Rw, meas_delta (IRLS weights at X) and Pw are honoured.
+ *   status_out  (B) 0, MHE_STATUS_NOT_SPD (a bad pivot of H, a non-finite Sigma or pivot of
+ *               it) or MHE_STATUS_BAD_CONSTANTS; the outputs of such a trajectory are NaN and
+ *               no other trajectory is affected.
+ *   scratch     mhe_kkt_cov_scratch_bytes(dims, batch, n_query) bytes (the query columns;
+ *               the border columns use the workspace); a smaller one is MHE_ERR_NULL.
+ * Dims without a border and without mixed rows are forwarded to mhe_state_cov (register path
+ * included; covz_out is not written): bitwise its result.
+ *
+ * mhe_kkt_arrival is mhe_kkt_cov with one query followed by mhe_arrival's inversion: x_arr,
+ * Pw_arr, cov_out as there, for mixed rows and extra variables.  n_eq > 0 returns
+ * MHE_ERR_UNSUPPORTED (an equality row between state components makes the block rank-
+ * deficient: it has no inverse), as does n > 40.  Scratch: mhe_kkt_cov_scratch_bytes(dims,
+ * batch, 1).  Both calls only enqueue work on `stream` and allocate nothing. */
+size_t mhe_kkt_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_query);
+int mhe_kkt_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at,
+                const double* PhiQ, int32_t n_query, double* cov_out, double* covz_out,
+                int32_t* status_out, void* scratch, size_t scratch_bytes, void* stream);
+int mhe_kkt_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
+                    double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
+                    size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Batched extended Kalman filter.

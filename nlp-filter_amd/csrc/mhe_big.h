@@ -165,6 +165,7 @@ struct BigArgs {
   int nq;
   double* cov;
   double* cov_scratch;
+  double* covz;      // k_big_kkt_cov: (B, nz, nz) covariance of the extra variables, or NULL
   const double* md;  // pseudo-Huber scale per measurement row (B|1, M) or NULL (mhe_solve_args.meas_delta)
   long long mdstride;
   const double* Pw;  // per-solve prior weight (B|1, n, n) or NULL = the constants' Pw (mhe_solve_args.Pw)
@@ -1810,6 +1811,39 @@ __device__ __forceinline__ double big_border_rhs(const BigArgs& a, const double*
   return base;
 }
 
+// LDL^T of the K x K quasi-definite Schur matrix of a bordered step (k_big_border,
+// k_big_kkt_cov), in place in Ms (row-major, lower triangle read and written; unit-lower L
+// below the diagonal, D on it) by ONE wavefront: right-looking, lanes over rows, no pivoting.
+// The pivot column is snapshotted into lc (K doubles) before the rank-1 update so no lane
+// reads an entry another lane has already scaled.  An exactly zero pivot -- an extra
+// variable no residual depends on: its row and column are exactly zero -- is held:
+// D_j = 0 marks it and its column of L is 0.
+__device__ __forceinline__ void big_ldl_factor(double* Ms, double* lc, int K, int lane) {
+  for (int j = 0; j < K; ++j) {
+    const double d = Ms[j * K + j];
+    const bool skip = d == 0.0;
+    for (int i = j + 1 + lane; i < K; i += 64) lc[i] = Ms[i * K + j];
+    wave_lds_sync();
+    for (int i = j + 1 + lane; i < K; i += 64) {
+      const double l = skip ? 0.0 : lc[i] / d;
+      for (int c = j + 1; c <= i; ++c) Ms[i * K + c] -= l * lc[c];
+      Ms[i * K + j] = l;  // unit-lower L below the diagonal
+    }
+    if (lane == 0 && skip) Ms[j * K + j] = 0.0;  // D_j = 0 marks a held variable
+    wave_lds_sync();
+  }
+}
+// One right-hand side through that factor, in place, by one lane: L y = r, D, L^T w = y;
+// a held variable's component is 0.  Element i of the right-hand side is r[i rs] (rs > 1:
+// a column of a row-major block of right-hand sides, one lane per column).
+__device__ __forceinline__ void big_ldl_solve(const double* Ms, double* r, int K, int rs) {
+  for (int i = 0; i < K; ++i)  // L y = r
+    for (int c = 0; c < i; ++c) r[i * rs] -= Ms[i * K + c] * r[c * rs];
+  for (int i = 0; i < K; ++i) r[i * rs] = Ms[i * K + i] != 0.0 ? r[i * rs] / Ms[i * K + i] : 0.0;
+  for (int i = K - 1; i >= 0; --i)  // L^T w = y
+    for (int c = i + 1; c < K; ++c) r[i * rs] -= Ms[c * K + i] * r[c * rs];
+}
+
 template <int n, int p>
 __global__ __launch_bounds__(BIG_NTHREADS) void k_big_border(BigArgs a) {
   constexpr int NZX = MHE_MAX_EXTRA;
@@ -1944,33 +1978,11 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_border(BigArgs a) {
   }
   __syncthreads();
 
-  // (4) LDL^T (right-looking, lanes over rows) and the solve, wave 0
+  // (4) LDL^T (right-looking, lanes over rows) and the solve, wave 0.  A NaN pivot
+  //     propagates into the step and the trajectory fails the finiteness test in k_big_update.
   if (wave == 0) {
-    // lower triangle only; the pivot column is snapshotted into lc before the
-    // rank-1 update so no lane reads an entry another lane has already scaled
-    for (int j = 0; j < K; ++j) {
-      const double d = Ms[j * K + j];
-      // exactly zero pivot: an extra variable no residual depends on (its row and
-      // column are exactly zero) -- held fixed.  A NaN pivot propagates into the
-      // step and the trajectory fails the finiteness test in k_big_update.
-      const bool skip = d == 0.0;
-      for (int i = j + 1 + lane; i < K; i += 64) lc[i] = Ms[i * K + j];
-      wave_lds_sync();
-      for (int i = j + 1 + lane; i < K; i += 64) {
-        const double l = skip ? 0.0 : lc[i] / d;
-        for (int c = j + 1; c <= i; ++c) Ms[i * K + c] -= l * lc[c];
-        Ms[i * K + j] = l;  // unit-lower L below the diagonal
-      }
-      if (lane == 0 && skip) Ms[j * K + j] = 0.0;  // D_j = 0 marks a held variable
-      wave_lds_sync();
-    }
-    if (lane == 0) {
-      for (int i = 0; i < K; ++i)  // L y = r
-        for (int c = 0; c < i; ++c) rw[i] -= Ms[i * K + c] * rw[c];
-      for (int i = 0; i < K; ++i) rw[i] = Ms[i * K + i] != 0.0 ? rw[i] / Ms[i * K + i] : 0.0;
-      for (int i = K - 1; i >= 0; --i)  // L^T w = y
-        for (int c = i + 1; c < K; ++c) rw[i] -= Ms[c * K + i] * rw[c];
-    }
+    big_ldl_factor(Ms, lc, K, lane);
+    if (lane == 0) big_ldl_solve(Ms, rw, K, 1);
   }
   __syncthreads();
 
@@ -1995,6 +2007,50 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_border(BigArgs a) {
 // rounded up to 16) -- BM / ZM are sized by the border and empty here.  use_env: the
 // split factorization's envelope is valid (big_env_first); tiles left of a row's first
 // column are exact zeros and are skipped, as the factorization skipped them.
+//
+// big_fwd_panel: one 16-column panel Zp (column-major, column stride dp) through L^-1 in
+// place, by the whole workgroup (Y_k = L_kk^-1 Z_k on wave 0; Z_I -= L_Ik Y_k, waves over
+// I).  MFMA operand layout as in k_big_border: A[i = l&15][m = 4r + (l>>4)],
+// B[m][j = l&15], C[(l>>4) + 4r][l&15].  FI: each tile row's first tile column, or nullptr.
+__device__ __forceinline__ void big_fwd_panel(double* Zp, const double* H, const double* LT, const int* FI, int NT,
+                                              int dp, int lane, int wave) {
+  const int ii = lane & 15, mg = lane >> 4;
+  auto zload = [&](int blk, int r) { return Zp[(size_t)ii * dp + 16 * blk + 4 * r + mg]; };  // B[m][j]
+  for (int k = 0; k < NT; ++k) {
+    if (wave == 0) {
+      d4 c = {0.0, 0.0, 0.0, 0.0};
+      double av[4], bv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        av[r] = LT[(size_t)k * DTS + (4 * r + mg) * LIS + ii];  // (L^-1)[i][m] = (L^-T)[m][i]
+        bv[r] = zload(k, r);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * k + mg + 4 * r] = c[r];
+    }
+    __syncthreads();
+    for (int I = k + 1 + wave; I < NT; I += BIG_NW) {
+      if (FI && k < FI[I]) continue;  // outside the envelope: L_Ik = 0
+      const double* L = H + (size_t)big_tile_index(I, k, NT) * 256;
+      d4 c;
+      double av[4], bv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        c[r] = Zp[(size_t)ii * dp + 16 * I + mg + 4 * r];
+        av[r] = L[(4 * r + mg) * 16 + ii];  // L_Ik[i][m], k-major tile (negated by the MFMA)
+        bv[r] = zload(k, r);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, MFMA_NEG_A);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * I + mg + 4 * r] = c[r];
+    }
+    __syncthreads();
+  }
+}
+
 template <int n>
 __global__ __launch_bounds__(BIG_NTHREADS) void k_big_cov(BigArgs a, int use_env) {
   const int b = blockIdx.x;
@@ -2020,46 +2076,7 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_cov(BigArgs a, int use_env
   }
   __syncthreads();
 
-  // MFMA operand layout as in k_big_border: A[i = l&15][m = 4r + (l>>4)], B[m][j = l&15],
-  // C[(l>>4) + 4r][l&15]
-  const int ii = lane & 15, mg = lane >> 4;
-  for (int p0 = 0; p0 < KQ; p0 += 16) {
-    double* Zp = ZQ + (size_t)p0 * dp;
-    auto zload = [&](int blk, int r) { return Zp[(size_t)ii * dp + 16 * blk + 4 * r + mg]; };  // B[m][j]
-    for (int k = 0; k < NT; ++k) {  // Y_k = L_kk^-1 Z_k;  Z_I -= L_Ik Y_k
-      if (wave == 0) {
-        d4 c = {0.0, 0.0, 0.0, 0.0};
-        double av[4], bv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          av[r] = LT[(size_t)k * DTS + (4 * r + mg) * LIS + ii];  // (L^-1)[i][m] = (L^-T)[m][i]
-          bv[r] = zload(k, r);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * k + mg + 4 * r] = c[r];
-      }
-      __syncthreads();
-      for (int I = k + 1 + wave; I < NT; I += BIG_NW) {
-        if (FI && k < FI[I]) continue;  // outside the envelope: L_Ik = 0
-        const double* L = H + (size_t)big_tile_index(I, k, NT) * 256;
-        d4 c;
-        double av[4], bv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          c[r] = Zp[(size_t)ii * dp + 16 * I + mg + 4 * r];
-          av[r] = L[(4 * r + mg) * 16 + ii];  // L_Ik[i][m], k-major tile (negated by the MFMA)
-          bv[r] = zload(k, r);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[r], bv[r], c, 0, 0, MFMA_NEG_A);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Zp[(size_t)ii * dp + 16 * I + mg + 4 * r] = c[r];
-      }
-      __syncthreads();
-    }
-  }
+  for (int p0 = 0; p0 < KQ; p0 += 16) big_fwd_panel(ZQ + (size_t)p0 * dp, H, LT, FI, NT, dp, lane, wave);
 
   // Cov_q[ra][cb] = Z_(q,ra) . Z_(q,cb): one wave per upper-triangle entry, mirrored
   for (int t = wave; t < nq * n * n; t += BIG_NW) {
@@ -2074,6 +2091,165 @@ __global__ __launch_bounds__(BIG_NTHREADS) void k_big_cov(BigArgs a, int use_env
       cov[(size_t)q * n * n + ra * n + cb] = s;
       cov[(size_t)q * n * n + cb * n + ra] = s;
     }
+  }
+}
+
+// ------------------------------------------------------------ covariance under a border
+// The covariance of the estimate of a bordered problem (extra variables z, equality rows
+// C v = r; mhe_kkt_cov) is the leading block of the inverse of the step's own KKT matrix
+//   [H  Bd; Bd^T  G],  Bd = [H_xz  C^T] (dp x K),  G = diag(H_zz, 0).
+// With Z_q = L^-1 S_q^T (k_big_cov's columns), V = L^-1 Bd (the forward half of
+// k_big_border's sweep), Sigma = G - V^T V (the Schur matrix k_big_border factors) and
+// T_q = V^T Z_q (K x n), block elimination gives
+//   Cov[x(t_q)] = Z_q^T Z_q + T_q^T Sigma^-1 T_q,     Cov[z] = (Sigma^-1)[0:nz, 0:nz]
+// (the constraint block of Sigma is negative definite: equality rows take variance away;
+// the z block is the positive definite Schur complement of H in [H H_xz; H_zx H_zz]).
+// The border is big_border_col / big_border_s of the assembled iterate, Sigma goes through
+// big_ldl_factor / big_ldl_solve as in the step: a held z (D_j = 0) is out of the system,
+// its row and column of Cov[z] are NaN.  The query columns live in the caller's scratch
+// as for k_big_cov, V in the workspace's ZM (BM is not needed: forward sweep only).  Every
+// block is formed from its upper triangle and mirrored.  A non-finite Sigma or pivot:
+// MHE_STATUS_NOT_SPD and NaN outputs for this trajectory.
+// Dynamic LDS (big_kkt_cov_lds doubles): Sigma K x K, the pivot column K, T_q and
+// Sigma^-1 T_q (K x n each; the latter also holds the nz unit columns for Cov[z]).
+__host__ __device__ inline int big_kkt_cov_lds(int K, int n, int nz) {
+  return K * K + K + K * n + K * (n > nz ? n : nz);
+}
+template <int n, int p>
+__global__ __launch_bounds__(BIG_NTHREADS) void k_big_kkt_cov(BigArgs a, int use_env) {
+  const int b = blockIdx.x;
+  const int nq = a.nq, KQ = nq * n, KPQ = (KQ + 15) / 16 * 16;
+  const int nz = a.nz, nc = a.nc, K = nz + nc, KP = (K + 15) / 16 * 16;
+  double* cov = a.cov + (size_t)b * nq * n * n;
+  double* covz = a.covz ? a.covz + (size_t)b * nz * nz : nullptr;
+  auto no_result = [&]() {
+    for (int t = threadIdx.x; t < nq * n * n; t += BIG_NTHREADS) cov[t] = NAN;
+    if (covz)
+      for (int t = threadIdx.x; t < nz * nz; t += BIG_NTHREADS) covz[t] = NAN;
+  };
+  if (a.state[b] != BIG_RUNNING) {  // bad constants / bad pivot of H: no result
+    no_result();
+    return;
+  }
+  const BigConst CL = big_const_layout(a.P, a.M, n, p, nc);  // p: the Rw section size
+  const BigWs WL = big_ws_layout(a.P, a.M, n, a.NT, nz, nc);
+  double* ws = a.ws + (size_t)b * a.ws_stride;
+  const double* H = ws + WL.H;
+  const double* LT = ws + WL.LT;
+  double* ZM = ws + WL.ZM;
+  const double* PhiE = (const double*)(a.cbuf + CL.PhiE);
+  const int* eq = (const int*)(a.cbuf + CL.eq);
+  const int E = a.M > 0 ? *(const int*)(a.cbuf + CL.ne) : 0;
+  const int NT = a.NT, Pp = a.Pp, dp = 16 * NT;
+  double* ZQ = a.cov_scratch + (size_t)b * KPQ * dp;
+  const int* FI = use_env ? big_env_first(ws, WL, n) : nullptr;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  double* Ms = sm;           // K x K: Sigma (lower triangle), then its LDL^T
+  double* lc = Ms + K * K;   // K: pivot column of the current LDL^T step
+  double* Tq = lc + K;       // K x n: T_q = V^T Z_q
+  double* Wq = Tq + K * n;   // K x max(n, nz): Sigma^-1 T_q; first Sigma^-1 [I_nz; 0]
+  __shared__ int bad;
+  if (threadIdx.x == 0) bad = 0;
+
+  // (a) query columns (as k_big_cov) and border columns (as k_big_border), component-major
+  //     rows; the panels' padding columns are zero
+  for (int t = threadIdx.x; t < KPQ * dp; t += BIG_NTHREADS) {
+    const int col = t / dp, r = t - col * dp, ca = r / Pp, j = r - ca * Pp;
+    const int q = col / n, c = col - q * n;
+    ZQ[t] = (col < KQ && c == ca && j < a.P) ? a.PhiQ[(size_t)q * a.P + j] : 0.0;
+  }
+  for (int t = threadIdx.x; t < KP * dp; t += BIG_NTHREADS) {
+    const int col = t / dp, r = t - col * dp, ca = r / Pp, j = r - ca * Pp;
+    ZM[t] = big_border_col(a, ws, WL, PhiE, eq, E, n, col, ca, j);
+  }
+  __syncthreads();
+
+  // (b) [Z | V] = L^-1 [S^T | Bd]
+  for (int p0 = 0; p0 < KQ; p0 += 16) big_fwd_panel(ZQ + (size_t)p0 * dp, H, LT, FI, NT, dp, lane, wave);
+  for (int p0 = 0; p0 < K; p0 += 16) big_fwd_panel(ZM + (size_t)p0 * dp, H, LT, FI, NT, dp, lane, wave);
+
+  // (c) Sigma = G - V^T V, lower triangle (what the LDL^T and the solve read)
+  for (int t = wave; t < K * K; t += BIG_NW) {
+    const int r = t / K, c = t - r * K;
+    if (c > r) continue;
+    const double* x = ZM + (size_t)r * dp;
+    const double* y = ZM + (size_t)c * dp;
+    double s = 0.0;
+    for (int i = lane; i < dp; i += 64) s += x[i] * y[i];
+    s = wave_sum(s);
+    if (lane == 0) {
+      const double v = big_border_s(a, ws, WL, E, r, c) - s;
+      Ms[r * K + c] = v;
+      if (!(fabs(v) < INFINITY)) bad = 1;
+    }
+  }
+  __syncthreads();
+
+  // (d) LDL^T with the zero-pivot hold, one wavefront
+  if (wave == 0) {
+    big_ldl_factor(Ms, lc, K, lane);
+    for (int j = lane; j < K; j += 64)
+      if (!(fabs(Ms[j * K + j]) < INFINITY)) bad = 1;
+  }
+  __syncthreads();
+  if (bad) {
+    no_result();
+    if (threadIdx.x == 0) a.state[b] = MHE_STATUS_NOT_SPD;
+    return;
+  }
+
+  // Cov[z]: the nz unit columns through the factor, one lane per column
+  if (covz) {
+    for (int t = threadIdx.x; t < K * nz; t += BIG_NTHREADS) Wq[t] = (t / nz == t % nz) ? 1.0 : 0.0;
+    __syncthreads();
+    if (threadIdx.x < nz) big_ldl_solve(Ms, Wq + threadIdx.x, K, nz);
+    __syncthreads();
+    for (int t = threadIdx.x; t < nz * nz; t += BIG_NTHREADS) {
+      const int r = t / nz, c = t - r * nz;
+      if (r > c) continue;
+      const bool held = Ms[r * K + r] == 0.0 || Ms[c * K + c] == 0.0;  // nothing is known about a held z
+      const double v = held ? NAN : Wq[r * nz + c];
+      covz[r * nz + c] = v;
+      covz[c * nz + r] = v;
+    }
+    __syncthreads();
+  }
+
+  for (int q = 0; q < nq; ++q) {
+    // T_q[k][c] = V_k . Z_(q,c): one wave per entry
+    for (int t = wave; t < K * n; t += BIG_NW) {
+      const int k = t / n, c = t - k * n;
+      const double* x = ZM + (size_t)k * dp;
+      const double* y = ZQ + (size_t)(q * n + c) * dp;
+      double s = 0.0;
+      for (int i = lane; i < dp; i += 64) s += x[i] * y[i];
+      s = wave_sum(s);
+      if (lane == 0) {
+        Tq[t] = s;
+        Wq[t] = s;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < n) big_ldl_solve(Ms, Wq + threadIdx.x, K, n);  // Sigma^-1 T_q, one lane per column
+    __syncthreads();
+    // Cov_q[ra][cb] = Z_(q,ra) . Z_(q,cb) + T_q[:, ra] . (Sigma^-1 T_q)[:, cb], upper triangle, mirrored
+    for (int t = wave; t < n * n; t += BIG_NW) {
+      const int ra = t / n, cb = t - ra * n;
+      if (ra > cb) continue;
+      const double* x = ZQ + (size_t)(q * n + ra) * dp;
+      const double* y = ZQ + (size_t)(q * n + cb) * dp;
+      double s = 0.0;
+      for (int i = lane; i < dp; i += 64) s += x[i] * y[i];
+      s = wave_sum(s);
+      if (lane == 0) {
+        double u = 0.0;
+        for (int k = 0; k < K; ++k) u += Tq[k * n + ra] * Wq[k * n + cb];
+        cov[(size_t)q * n * n + ra * n + cb] = s + u;
+        cov[(size_t)q * n * n + cb * n + ra] = s + u;
+      }
+    }
+    __syncthreads();  // Tq / Wq are reused by the next query
   }
 }
 

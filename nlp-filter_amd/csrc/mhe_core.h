@@ -2875,10 +2875,28 @@ inline int launch_big_resid(const BigArgs& A, int batch, int final_pass, hipStre
 // BIG_STAGE_COV (mhe_state_cov) runs both at A.X -- the factorization plan a solve would
 // pick -- and then k_big_cov: the query columns A.PhiQ through the factor, A.cov.
 // The state words are set by the caller.
-constexpr int BIG_STAGE_ASSEMBLE = 0, BIG_STAGE_FACTOR = 1, BIG_STAGE_COV = 2;
+// BIG_STAGE_KKT_COV (mhe_kkt_cov) is BIG_STAGE_COV for any large-system problem: with a
+// border (A.nz + A.nc > 0) the last launch is k_big_kkt_cov -- the step's own border through
+// the factor and its Schur complement, A.cov and A.covz -- else k_big_cov as it is.
+constexpr int BIG_STAGE_ASSEMBLE = 0, BIG_STAGE_FACTOR = 1, BIG_STAGE_COV = 2, BIG_STAGE_KKT_COV = 3;
+constexpr int BIG_LDS_LIMIT = 64 * 1024;  // k_big_kkt_cov's dynamic LDS (K = MHE_MAX_EQ, n = 40: 49 KB)
 template <class DYN, class MEAS>
 int launch_big_stage(const mhe_dims* dm, BigArgs& A, int batch, int stage, hipStream_t st) {
-  if (stage == BIG_STAGE_COV) {
+  if (stage == BIG_STAGE_KKT_COV && A.nz + A.nc > 0) {
+    const int smem_c = big_kkt_cov_lds(A.nz + A.nc, DYN::n, A.nz) * (int)sizeof(double);
+    if (smem_c > BIG_LDS_LIMIT) return MHE_ERR_UNSUPPORTED;  // checked before anything is enqueued
+    void (*kern)(BigArgs, int) = k_big_kkt_cov<DYN::n, MEAS::p>;
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem_c) != hipSuccess)
+      return MHE_ERR_HIP;
+    int rc = launch_big_stage<DYN, MEAS>(dm, A, batch, BIG_STAGE_ASSEMBLE, st);
+    if (rc != MHE_OK) return rc;
+    BigCholPlan cp;
+    if (big_chol_plan(A, cp, true) < 0) return MHE_ERR_HIP;  // refined pivots, as BIG_STAGE_COV
+    launch_big_factor(cp, A, batch, st);
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(BIG_NTHREADS), smem_c, st, A, cp.split ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  }
+  if (stage == BIG_STAGE_COV || stage == BIG_STAGE_KKT_COV) {
     if (A.nz + A.nc > 0) return MHE_ERR_UNSUPPORTED;
     int rc = launch_big_stage<DYN, MEAS>(dm, A, batch, BIG_STAGE_ASSEMBLE, st);
     if (rc != MHE_OK) return rc;

@@ -810,6 +810,82 @@ int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_arg
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
+// mixed rows, extra variables or equality rows: the problems mhe_state_cov / mhe_arrival refuse
+static bool is_general(const mhe_dims* dims) {
+  return dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED;
+}
+
+size_t mhe_kkt_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_query) {
+  // the query columns, as mhe_state_cov's; the border columns live in the workspace (ZM)
+  return mhe_cov_scratch_bytes(dims, batch, n_query);
+}
+
+int mhe_kkt_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* PhiQ,
+                int32_t n_query, double* cov_out, double* covz_out, int32_t* status_out, void* scratch,
+                size_t scratch_bytes, void* stream) {
+  int NT = 0;
+  int rc = check_dims(dims, &NT);
+  if (rc != MHE_OK) return rc;
+  if (!is_general(dims))  // no border, typed rows: mhe_state_cov itself (both paths)
+    return mhe_state_cov(dims, const_buf, at, PhiQ, n_query, cov_out, status_out, scratch, scratch_bytes, stream);
+  if (!is_big(dims)) return MHE_ERR_UNSUPPORTED;  // every general problem takes the large-system path
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  const int batch = at->batch;
+  if (batch < 0 || n_query <= 0) return MHE_ERR_DIMS;
+  if (!PhiQ || !cov_out || !status_out) return MHE_ERR_NULL;
+  if (batch == 0) return MHE_OK;
+  if (!const_buf || !at->X0 || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) || (dims->q > 0 && !at->PAR) ||
+      (dims->has_prior && !at->x0) || (dims->n_extra > 0 && !at->Z0))
+    return MHE_ERR_NULL;
+  rc = check_row_args(dims, at->Rw, at->meas_delta);  // as mhe_solve
+  if (rc == MHE_OK) rc = check_pw_arg(dims, at->Pw);
+  if (rc != MHE_OK) return rc;
+  const PairOps* ops = find_pair(dims);
+  if (!ops) return MHE_ERR_UNSUPPORTED;
+  if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
+  if (!scratch || scratch_bytes < mhe_kkt_cov_scratch_bytes(dims, batch, n_query)) return MHE_ERR_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
+  A.n_bounds = 0;  // the GN model at X under its equality rows (bounds are not reflected)
+  A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
+  A.Rw = at->Rw; A.rwstride = at->rw_bstride; A.md = at->meas_delta; A.mdstride = at->md_bstride;
+  A.Pw = at->Pw; A.pwstride = at->pw_bstride;
+  A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
+  A.Z =const_cast<double*>(at->Z0);  // read only by k_big_resid
+  A.cost = (double*)scratch; A.state = status_out;
+  A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
+  A.covz = dims->n_extra > 0 ? covz_out : nullptr;
+  const int nb = (batch + 255) / 256;
+  hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
+  rc = ops->big_stage(dims, A, batch, BIG_STAGE_KKT_COV, st);
+  if (rc != MHE_OK) return rc;
+  hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status_out);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
+int mhe_kkt_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
+                    double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  int NT = 0;
+  int rc = check_dims(dims, &NT);
+  if (rc != MHE_OK) return rc;
+  // an equality row between state components makes the block rank-deficient: no inverse
+  if (dims->n_eq > 0 || dims->n > ARR_NMAX) return MHE_ERR_UNSUPPORTED;
+  if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_arrival
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  if (at->batch < 0) return MHE_ERR_DIMS;
+  if (!phi || !x_arr || !Pw_arr || !status_out) return MHE_ERR_NULL;
+  if (at->batch == 0) return MHE_OK;
+  double* cov = cov_out ? cov_out : Pw_arr;  // as mhe_arrival: k_arrival inverts in place
+  rc = mhe_kkt_cov(dims, const_buf, at, phi, 1, cov, nullptr, status_out, scratch, scratch_bytes, stream);
+  if (rc != MHE_OK) return rc;
+  hipLaunchKernelGGL(k_arrival, dim3(at->batch), dim3(64), 0, (hipStream_t)stream, dims->n, dims->N + 1, at->batch,
+                     at->X0, phi, cov, Pw_arr, x_arr, status_out);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
 int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
                int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, double* W, double* F,
                double* E, double* Hm, void* stream) {

@@ -96,6 +96,11 @@ SIGNATURES = {
     "mhe_arrival_scratch_bytes": (c_sz, [_P, c_i32]),
     "mhe_arrival": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                    c_vp]),
+    "mhe_kkt_cov_scratch_bytes": (c_sz, [_P, c_i32, c_i32]),
+    "mhe_kkt_cov": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                   c_vp]),
+    "mhe_kkt_arrival": (ctypes.c_int, [_P, c_vp, ctypes.POINTER(MheSolveArgs), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_sz, c_vp]),
     "mhe_ekf_run": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

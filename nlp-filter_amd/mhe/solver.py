@@ -538,8 +538,22 @@ class BatchSolver:
                 np.asarray(t, dtype=np.float64).reshape(-1))
         return np.asarray(Phi.cpu() if isinstance(Phi, torch.Tensor) else Phi, dtype=np.float64).reshape(-1, self.P)
 
+    @property
+    def general(self):
+        """True for mixed rows, extra variables or equality rows: covariance() and arrival()
+        then go through mhe_kkt_cov / mhe_kkt_arrival (the bordered system's inverse)."""
+        return self.meas_name == "mixed" or self.n_extra > 0 or self.n_eq > 0
+
+    def _z(self, Z, B):
+        """The extra variables (B, n_extra) a general solver's covariance is formed at."""
+        if not self.n_extra:
+            return None
+        if Z is None:
+            raise ValueError("this problem has extra variables: pass Z (B, n_extra), the solve's fifth output")
+        return _dev(Z, self.device, (B, self.n_extra))
+
     def arrival(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, meas_delta=None, Pw=None, stream=None,
-                with_cov=False):
+                with_cov=False, Z=None):
         """Arrival cost of the window shifted to the query time (mhe_arrival): with the
         covariance block C = S_t H^-1 S_t^T of ``covariance()`` at X (same inputs, the window's
         own ``Pw`` included), x_arr (B, n) = x(t) by the Lagrange row in node order and
@@ -549,7 +563,9 @@ class BatchSolver:
         needs no copy -- and C (B, n, n) as a fourth element with ``with_cov`` (bitwise
         ``covariance(..., t=[t])[0][:, 0]``).  status (B,): 0, 2 = not SPD (H or the block), 4 =
         bad constants; the outputs of such a trajectory are NaN, the others unaffected.
-        Refusals as ``covariance()``."""
+        Refusals as ``covariance()``.  A general solver (mixed rows, extra variables: ``Z`` the
+        solve's (B, n_extra)) goes through mhe_kkt_arrival; with equality rows the block is
+        rank-deficient and the call is refused (MHE_ERR_UNSUPPORTED)."""
         self._check_ready()
         Phi = self._query_rows(t, Phi)
         if Phi.shape[0] != 1:
@@ -560,6 +576,9 @@ class BatchSolver:
             md_t, mstr = self._md(meas_delta, B)
             Pw_t, wstr = self._pw(Pw, B)
             phi = _dev(Phi, self.device)
+            Z_t = self._z(Z, B)
+            call, cname = ((self.lib.mhe_kkt_arrival, "mhe_kkt_arrival") if self.general else
+                           (self.lib.mhe_arrival, "mhe_arrival"))
             n, P, M = self.n, self.P, self.M
             f64 = dict(dtype=torch.float64, device=self.device)
             x_arr = torch.empty((B, n), **f64)
@@ -568,12 +587,13 @@ class BatchSolver:
             status = torch.empty(B, dtype=torch.int32, device=self.device)
             chunk = max(1, self._chunk(B, s))  # streamed in chunks like covariance()
             ws, nb = self._workspace(chunk, s)
-            sb = self.lib.mhe_arrival_scratch_bytes(self.dims, chunk)
+            sb = (self.lib.mhe_kkt_cov_scratch_bytes(self.dims, chunk, 1) if self.general else
+                  self.lib.mhe_arrival_scratch_bytes(self.dims, chunk))
             scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
             for lo in range(0, B, chunk):
                 a = _lib.MheSolveArgs()
                 a.batch = min(chunk, B - lo)
-                a.X0 = _at(X, lo, P * n)
+                a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, self.n_extra)
                 a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
                 a.Y = _at(Y_t, lo, M * self.p)
                 a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
@@ -582,17 +602,17 @@ class BatchSolver:
                 a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
                 a.x0 = _at(x0_t, lo, n)
                 a.workspace, a.workspace_bytes = _ptr(ws), nb
-                rc = self.lib.mhe_arrival(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(phi), _at(x_arr, lo, n),
-                                          _at(Pw_arr, lo, n * n), _at(cov, lo, n * n), _at(status, lo, 1, 4),
-                                          _ptr(scratch), sb, _handle(s))
-                _lib.check(rc, "mhe_arrival")
-            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, phi, x_arr, Pw_arr, cov, status, ws, scratch)
+                rc = call(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(phi), _at(x_arr, lo, n),
+                          _at(Pw_arr, lo, n * n), _at(cov, lo, n * n), _at(status, lo, 1, 4), _ptr(scratch), sb, _handle(s))
+                _lib.check(rc, cname)
+            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, phi, x_arr, Pw_arr, cov, status, ws,
+                       scratch)
         if with_cov:
             return x_arr, Pw_arr, status, cov
         return x_arr, Pw_arr, status
 
     def covariance(self, X, U, Y, PAR=None, x0=None, t=None, Phi=None, Rw=None, stream=None, meas_delta=None,
-                   Pw=None):
+                   Pw=None, Z=None, with_extra=False):
         """Posterior covariance of the state at query times (mhe_state_cov): with H = J^T W J
         at X (the solve's own assembly: Huber weights, per-solve ``Rw``, the IRLS weights of
         ``meas_delta`` at X) and S_t = phi(t)^T (x)
@@ -601,9 +621,15 @@ class BatchSolver:
         extractSolution uses; or pass the basis rows ``Phi`` (Tq, P) directly.  Returns
         (cov (B, Tq, n, n), status (B,): 0, 2 = not SPD, 4 = bad constants; cov is NaN where
         status != 0).  The inverse of the half-Hessian: a covariance when the weights are
-        inverse covariances.  Bounds are not reflected; bordered and mixed-row problems are
-        refused (MHE_ERR_UNSUPPORTED).  ``Pw``: the per-solve prior weight, as for solve();
-        ``arrival()`` returns the inverse of one query's block without a host round trip."""
+        inverse covariances.  Bounds are not reflected.  ``Pw``: the per-solve prior weight, as
+        for solve(); ``arrival()`` returns the inverse of one query's block without a host round
+        trip.  A general solver (mixed rows, extra variables, equality rows) calls mhe_kkt_cov:
+        the covariance under the equality rows, the leading block of the bordered system's
+        inverse at (X, ``Z``) -- positive semi-definite with equality rows; ``Z`` (B, n_extra) is
+        the solve's fifth output.  ``with_extra``: return (cov, covz, status) with covz
+        (B, n_extra, n_extra) the extra variables' block (NaN row and column for a variable no
+        row depends on; None without extra variables).  A typed solver makes the mhe_state_cov
+        call whatever these two arguments are."""
         self._check_ready()
         Phi = self._query_rows(t, Phi)
         Tq = Phi.shape[0]
@@ -615,19 +641,24 @@ class BatchSolver:
             md_t, mstr = self._md(meas_delta, B)
             Pw_t, wstr = self._pw(Pw, B)
             PhiQ = _dev(Phi, self.device)
-            n, P, M = self.n, self.P, self.M
+            Z_t = self._z(Z, B) if self.general else None
+            n, P, M, nz = self.n, self.P, self.M, self.n_extra
+            covz = None
+            if self.general and with_extra and nz:
+                covz = torch.empty((B, nz, nz), dtype=torch.float64, device=self.device)
             cov = torch.empty((B, Tq, n, n), dtype=torch.float64, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
             # the large-system workspace and the query columns' scratch are streamed in
             # chunks like solve()'s, the outputs written in place at each chunk's offset
             chunk = max(1, self._chunk(B, s))
             ws, nb = self._workspace(chunk, s)
-            sb = self.lib.mhe_cov_scratch_bytes(self.dims, chunk, Tq)
+            sb = (self.lib.mhe_kkt_cov_scratch_bytes if self.general else self.lib.mhe_cov_scratch_bytes)(
+                self.dims, chunk, Tq)
             scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
             for lo in range(0, B, chunk):
                 a = _lib.MheSolveArgs()
                 a.batch = min(chunk, B - lo)
-                a.X0 = _at(X, lo, P * n)
+                a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, nz)
                 a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
                 a.Y = _at(Y_t, lo, M * self.p)
                 a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
@@ -636,11 +667,19 @@ class BatchSolver:
                 a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
                 a.x0 = _at(x0_t, lo, n)
                 a.workspace, a.workspace_bytes = _ptr(ws), nb
+                if self.general:
+                    rc = self.lib.mhe_kkt_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
+                                              _at(cov, lo, Tq * n * n), _at(covz, lo, nz * nz), _at(status, lo, 1, 4),
+                                              _ptr(scratch), sb, _handle(s))
+                    _lib.check(rc, "mhe_kkt_cov")
+                    continue
                 rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
                                             _at(cov, lo, Tq * n * n), _at(status, lo, 1, 4), _ptr(scratch), sb,
                                             _handle(s))
                 _lib.check(rc, "mhe_state_cov")
-            keep_alive(s, cur, X, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, PhiQ, cov, status, ws, scratch)
+            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, PhiQ, cov, covz, status, ws, scratch)
+        if with_extra:
+            return cov, covz, status
         return cov, status
 
     def chol_solve(self, H, g, stream=None):

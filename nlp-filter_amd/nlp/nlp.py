@@ -762,7 +762,8 @@ class fixedTimeOptimalEstimationNLP(NLP):
                         meas_delta=md, Pw=Pw)
         X, cost, iters, status = out[:4]
         # extractCovariance / extractArrivalCost
-        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, md=md, Pw=Pw, engine=eng)
+        self._last_solve = dict(U=U, Y=Y, PAR=PAR, x0=x0, Rw=Rw, md=md, Pw=Pw, engine=eng,
+                                Z=out[4] if eng.n_extra else None, extra=list(self._extra))
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         X = X.cpu().numpy()[0]
@@ -796,16 +797,21 @@ class fixedTimeOptimalEstimationNLP(NLP):
         (BatchSolver.covariance).  A covariance when Q, R and the prior weight are inverse
         covariances; the arrival cost of the next window (its inverse at the shift time,
         formed on the device) is ``extractArrivalCost``.  State bounds are not reflected.
-        Raises UnsupportedFeature for
-        problems with mixed rows / extra variables, constraints (a covariance under
-        constraints is a projected quantity), for a variable other than the state
-        trajectory, and before the first solve()."""
+        A general problem (mixed rows, extra variables, constraint rows) uses that solve's
+        engine, extra variables and per-solve inputs: the covariance under the engine's
+        equality rows (positive semi-definite then), the leading block of the bordered
+        system's inverse.  After an active-set solve these are the addEqConstraint rows plus
+        the inequality rows (and bounds) ACTIVE at the last device solve, held as equalities:
+        the covariance of the estimate on that active set, not of the inequality-constrained
+        problem.  An extra variable's own block is ``extractVariableCovariance``.
+        Raises UnsupportedFeature for a variable other than the state trajectory and before
+        the first solve()."""
         eng, last = self._cov_engine(name, "extractCovariance")
         import torch
         X = np.stack([x.value for x in self._X])[None]
         Phi = self.CPM.lagrange_matrix(np.asarray(t_array, dtype=np.float64).reshape(-1))
         cov, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"],
-                                     meas_delta=last["md"], Pw=last["Pw"])
+                                     meas_delta=last["md"], Pw=last["Pw"], Z=last["Z"])
         torch.cuda.synchronize()
         st = int(status.cpu().numpy()[0])
         if st != 0:
@@ -820,27 +826,58 @@ class fixedTimeOptimalEstimationNLP(NLP):
             raise UnsupportedFeature(f"{what} needs a solve() first")
         if self._X is None or name != self._X[0].name:
             raise UnsupportedFeature(f"{what}: {name!r} is not the state trajectory")
-        eng = last["engine"]  # the engine of that solve (a re-set R or prior may have built another since)
-        if self._ineq or self._eq or self._active or eng.n_eq or eng.n_extra or eng.meas_name == "mixed":
-            raise UnsupportedFeature(f"{what}: general (mixed-row), active-set and bordered problems "
-                                     "have no unconstrained covariance")
-        return eng, last
+        return last["engine"], last  # the engine of that solve (a re-set R or prior may have built another since)
+
+    def extractVariableCovariance(self, name):
+        """Posterior covariance (k, k) of an extra decision variable of the last solve -- a
+        variable other than the state trajectory that measurement params reference, e.g. the
+        static receiver ``'xa'`` of multi-receiver.py -- its block of the bordered system's
+        inverse at the solution (BatchSolver.covariance(with_extra=True)), under the constraint
+        rows of that solve.  A component no cost term depends on has a NaN row and column.
+        Raises UnsupportedFeature before the first solve() and for a name that is not such a
+        variable."""
+        last = getattr(self, "_last_solve", None)
+        if self.sol is None or last is None:
+            raise UnsupportedFeature("extractVariableCovariance needs a solve() first")
+        eng = last["engine"]
+        hit = [(v, off) for v, off in last["extra"] if v.name == name]
+        if not hit:
+            raise UnsupportedFeature(f"extractVariableCovariance: {name!r} is not an extra decision variable of "
+                                     "the last solve (the state trajectory has extractCovariance)")
+        v, off = hit[0]
+        import torch
+        X = np.stack([x.value for x in self._X])[None]
+        _, covz, status = eng.covariance(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=np.eye(1, self.N + 1),
+                                         Rw=last["Rw"], meas_delta=last["md"], Pw=last["Pw"], Z=last["Z"],
+                                         with_extra=True)
+        torch.cuda.synchronize()
+        st = int(status.cpu().numpy()[0])
+        if st != 0:
+            warnings.warn(f"extractVariableCovariance: the system at the solution is not usable (status {st})")
+        return covz.cpu().numpy()[0][off:off + v.size, off:off + v.size]
 
     def extractArrivalCost(self, name, t):
         """The next window's prior from the last solve, for a horizon shifted by ``t``:
         (xhat (n,), Pw (n, n)) with xhat = x(t), what ``extractSolution(name, [t])[0]`` returns,
         and Pw = inv(extractCovariance(name, [t])[0]), bitwise symmetric -- both formed on the
         device (BatchSolver.arrival).  Feed them to setParameter: a Parameter-valued ``"Q"`` of
-        addInitialCost travels per solve, so the engine is not rebuilt.  Refusals as
-        extractCovariance."""
+        addInitialCost travels per solve, so the engine is not rebuilt.  Works for mixed rows
+        and extra variables (that solve's engine, z and per-solve inputs).  Refusals as
+        extractCovariance, and UnsupportedFeature for a problem with constraint rows (held
+        equality rows make the block rank-deficient: it has no inverse)."""
         eng, last = self._cov_engine(name, "extractArrivalCost")
+        if eng.n_eq:
+            raise UnsupportedFeature("extractArrivalCost: the covariance block under constraint rows is "
+                                     "rank-deficient (an equality row between state components leaves no "
+                                     "variance along it), so it has no inverse; the arrival cost under "
+                                     "equality rows needs a reduced-space weight")
         import torch
         X = np.stack([x.value for x in self._X])[None]
         Phi = self.CPM.lagrange_matrix(np.asarray(t, dtype=np.float64).reshape(-1))
         if Phi.shape[0] != 1:
             raise ValueError("extractArrivalCost takes one time")
         x_arr, Pw_arr, status = eng.arrival(X, last["U"], last["Y"], last["PAR"], last["x0"], Phi=Phi, Rw=last["Rw"],
-                                            meas_delta=last["md"], Pw=last["Pw"])
+                                            meas_delta=last["md"], Pw=last["Pw"], Z=last["Z"])
         torch.cuda.synchronize()
         st = int(status.cpu().numpy()[0])
         if st != 0:

@@ -142,12 +142,13 @@ typedef struct mhe_dims {
                            build time and part of its layout stamp (with eq_rhs):
                            solving with other rows than the buffer was built with
                            returns MHE_STATUS_BAD_CONSTANTS -- rebuild instead.     */
-  int32_t force_large;  /* 1: take the large-system path even when the problem fits
-                           the register-resident kernel (parity tests of the two
-                           paths on identical inputs).  The path is a function of
-                           dims alone; mhe_build_constants stamps it (with the
-                           layout-defining dims) into the constants buffer and every
-                           solve checks that stamp on the device.                 */
+  int32_t force_large;  /* path preference, MHE_PATH_* below.  MHE_PATH_LARGE: take the
+                           large-system path even when the problem fits the
+                           register-resident kernel (parity tests of the two paths on
+                           identical inputs).  MHE_PATH_FUSED_GENERAL: see below.  The
+                           path is a function of dims alone; mhe_build_constants stamps
+                           it (with the layout-defining dims) into the constants buffer
+                           and every solve checks that stamp on the device.        */
   double dyn_par[8];    /* static dynamics parameters (model-defined, e.g.
                            MHE_DYN_VEHICLE_GNSS); 0 for the parameter-free models   */
   const double* eq_rhs; /* HOST pointer, n_eq constants r_i of the rows
@@ -155,6 +156,30 @@ typedef struct mhe_dims {
                            Non-zero r: the rows an active set imposes (bounds and
                            inequality constraints held at equality by the host) */
 } mhe_dims;
+
+/* mhe_dims.force_large.  Any value other than AUTO and FUSED_GENERAL is LARGE.
+ *
+ * MHE_PATH_FUSED_GENERAL (MHE_HAS_FUSED_GENERAL) is a preference: a MHE_MEAS_MIXED problem
+ * (with or without n_extra / n_eq) runs the fused kernel k_gn_general -- one launch per batch,
+ * one workgroup per trajectory, no workspace -- when dyn_cost is MHE_COST_L2, n_bounds == 0,
+ * n <= 16, the node-major padded system 16 ceil(P n / 16) is at most 208 and the kernel's
+ * LDS layout fits (all functions of dims alone).  For every other dims, typed problems
+ * included, the value behaves as MHE_PATH_AUTO.  For such fused-general dims
+ *   mhe_workspace_bytes = 0, mhe_padded_dim = 16 ceil(P n / 16), mhe_kkt_dim = that + K,
+ *   mhe_const_bytes / mhe_build_constants use the fused layout (own stamp),
+ *   mhe_solve honours Z0, Rw, Pw and lambda_out and solves the same bordered GN steps as
+ *   the large-system path (other summation order: results agree to rounding, not bitwise);
+ *   mhe_solve with meas_delta, mhe_chol_solve_ws, mhe_kkt_cov, mhe_kkt_arrival and
+ *   mhe_resjac return MHE_ERR_UNSUPPORTED before any launch (as do the register-path
+ *   parity calls): build a second set of constants with MHE_PATH_AUTO for those.
+ * The kernel groups measurement rows by epoch (bitwise-identical Phi rows) in LDS;
+ * mhe_build_constants returns MHE_ERR_UNSUPPORTED when Phi has more distinct rows than the
+ * layout holds (it copies one word back and waits for the stream: the only build that
+ * synchronises) -- use MHE_PATH_AUTO then. */
+#define MHE_PATH_AUTO 0
+#define MHE_PATH_LARGE 1
+#define MHE_PATH_FUSED_GENERAL 2
+#define MHE_HAS_FUSED_GENERAL 1
 
 /* Dynamics cost (addDynamicsCost, nlp/nlp.py:242-245): */
 #define MHE_COST_L2 0     /* cost_functions.weighted_l2_norm  (cost_functions.py:20-22) */

@@ -1,5 +1,6 @@
 // libmhe core: the kernels of the batched collocation Gauss-Newton estimator
-// (register-resident path k_gn / k_gn_bounded, large-system path mhe_big.h)
+// (register-resident path k_gn / k_gn_bounded, large-system path mhe_big.h, the fused
+// solve of small mixed-row / bordered problems mhe_general.h)
 // and the host-side launch templates, shared by the translation units that
 // instantiate them per (dynamics, measurement) plug-in pair (pair_*.hip).
 // The C-ABI itself (include/mhe.h) lives in mhe_gn.hip.
@@ -190,6 +191,11 @@ struct GnArgs {
   long long mdstride;       //   read by the MHUBER instances only
   const double* Pw;         // per-solve prior weight (B|1, n, n) or NULL = the constants' Pw (mhe_solve_args.Pw);
   long long pwstride;       //   build_tiles adds Pw_b - Pw_const to the node-0 block that Cc carries
+  // k_gn_general only (mhe_general.h): the border of the KKT system
+  const double* Z0;         // (B, nz) extra variables at the start
+  double* Zout;             // (B, nz)
+  double* lam;              // (B, nc) or NULL: multipliers of the equality rows, last bordered step
+  int nz, nc;               // mhe_dims.n_extra / n_eq
 };
 
 // The prior weight of trajectory b: the per-solve block, or the constants' (a wave-uniform select)
@@ -943,16 +949,19 @@ __device__ __forceinline__ void build_slots_n2(const GnArgs& a, const ConstLayou
 // BOUNDED (projected Newton, k_gn_bounded): rows and columns of the epsilon-active
 // unknowns (ACT) are replaced by their diagonal entries -- the reduced GN system on
 // the free unknowns, a diagonally scaled gradient step on the active ones.
+// PhiL: the measurement basis rows (a.M x a.P) staged in LDS by the caller (k_gn_general's
+// epoch rows), or nullptr = the constants' Phi
 template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false, bool PW = true>
 __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
-                                            d4 (&acc)[SLOTS], int wave, int lane, int stab) {
+                                            d4 (&acc)[SLOTS], int wave, int lane, int stab,
+                                            const double* PhiL = nullptr) {
   const int* ACT = (const int*)(sm + SL.ACT);
   const double* Dm = (const double*)(a.cbuf + CL.D);
   const double* LAM = sm + SL.LAM;
   const double* Cc = (const double*)(a.cbuf + CL.Cc);
   const double* DA = (const double*)(a.cbuf + CL.DA);
   const double* DB = (const double*)(a.cbuf + CL.DB);
-  const double* Phi = (const double*)(a.cbuf + CL.Phi);
+  const double* Phi = PhiL ? PhiL : (const double*)(a.cbuf + CL.Phi);
   const double* Es = sm + SL.Es;
   const double* FtE = sm + SL.FtE;
   const double* G = sm + SL.G;
@@ -1767,16 +1776,20 @@ __device__ __forceinline__ void block_back(const double* LT, double* yv, int lan
 // U_Jb delta_b from y_J (row sums over the 16 lanes of a DPP row); the owner of
 // (b-1, b) then finishes y_{b-1} and forms delta_{b-1} = L^-T y_{b-1} itself.
 // One workgroup barrier per block.
-template <int SLOTS>
+// YLAST: the caller has formed y_{NT-1} already (k_gn_general: the bordered step corrects
+// all of y between the factorization and this solve)
+template <int SLOTS, bool YLAST = false>
 __device__ __forceinline__ void backward(const GnArgs& a, const SmemLayout& SL, double* sm,
                                          d4 (&acc)[SLOTS], int wave, int lane, int stab) {
   const double* DT = sm + SL.DT;
   double* DV = sm + SL.YV;
   const int NT = a.NT;
   if (wave == (NT - 1) % NW) {
-    const double* BV = sm + SL.BV;
-    block_fwd(DT + (NT - 1) * DTS, BV + 16 * (NT - 1), DV + 16 * (NT - 1), lane);  // y_{NT-1}
-    wave_lds_sync();
+    if constexpr (!YLAST) {
+      const double* BV = sm + SL.BV;
+      block_fwd(DT + (NT - 1) * DTS, BV + 16 * (NT - 1), DV + 16 * (NT - 1), lane);  // y_{NT-1}
+      wave_lds_sync();
+    }
     block_back(DT + (NT - 1) * DTS, DV + 16 * (NT - 1), lane);
   }
   __syncthreads();
@@ -1942,6 +1955,65 @@ __device__ __forceinline__ int opaque_s(int x) {
 //                         U[4r + (l>>4)][l&15]), Y_k's the B operand -- 4 MFMAs, NEG_A.
 // One workgroup barrier per block row.  A panel column's results depend on that column
 // alone, so a query's block does not depend on which other queries share the call.
+//
+// fwd_sweep_panel is that sweep for one panel, shared with the bordered step of k_gn_general
+// (mhe_general.h), which needs the swept columns themselves: STORE = false (cov_sweep) adds
+// Y_k^T Y_k to the caller's Gram part; STORE = true leaves Y_k in the panel's block k instead
+// (written by wave k % NW after the step's barrier: nobody reads Z_k again).
+template <int SLOTS, bool STORE>
+__device__ __forceinline__ void fwd_sweep_panel(int NT, const double* DT, double* ZP, d4 (&acc)[SLOTS], int wave,
+                                                int lane, int stab, d4& gram) {
+#pragma unroll 1
+  for (int k = 0; k < NT; ++k) {
+    int lane_o = lane, wave_o = wave, stab_o = stab;  // opaque per step, as factor_forward
+    asm volatile("" : "+v"(lane_o));
+    asm volatile("" : "+s"(wave_o));
+    asm volatile("" : "+v"(stab_o));
+    const int sT = slot_start(k, wave_o, NT), sU = slot_start(k + 1, wave_o, NT);
+    const unsigned mT = (1u << sU) - (1u << sT);  // this wave's tiles (k, b), b > k
+    const bool own = wave_o == k % NW;
+    [[maybe_unused]] d4 ykeep = {0.0, 0.0, 0.0, 0.0};
+    if (mT != 0u || own) {
+      const double* LT = DT + k * DTS;
+      double la[4], zk[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        la[r] = LT[(4 * r + (lane_o >> 4)) * LIS + (lane_o & 15)];  // L^-1[l&15][4r+(l>>4)]
+        zk[r] = ZP[k * 256 + r * 64 + lane_o];
+      }
+      d4 y = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) y = __builtin_amdgcn_mfma_f64_16x16x4f64(la[r], zk[r], y, 0, 0, 0);
+      if constexpr (STORE) {
+        ykeep = y;
+      } else if (own) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gram = __builtin_amdgcn_mfma_f64_16x16x4f64(y[r], y[r], gram, 0, 0, 0);
+      }
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s) {
+        if ((mT >> s) & 1u) {
+          double* zb = ZP + (slot_ij(stab_o, s) & 0xffff) * 256 + lane_o;
+          d4 t;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t[r] = zb[64 * r];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[s][r], y[r], t, 0, 0, MFMA_NEG_A);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) zb[64 * r] = t[r];
+        }
+      }
+    }
+    __syncthreads();  // Z_{k+1} complete; nobody reads Z_k again
+    if constexpr (STORE) {
+      if (own) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ZP[k * 256 + r * 64 + lane_o] = ykeep[r];
+      }
+    }
+  }
+}
+
 template <int n, int SLOTS>
 __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL, double* sm, d4 (&acc)[SLOTS],
                                           int wave, int lane, int stab, int b) {
@@ -1959,46 +2031,7 @@ __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL,
     }
     __syncthreads();
     d4 gram = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-    for (int k = 0; k < NT; ++k) {
-      int lane_o = lane, wave_o = wave, stab_o = stab;  // opaque per step, as factor_forward
-      asm volatile("" : "+v"(lane_o));
-      asm volatile("" : "+s"(wave_o));
-      asm volatile("" : "+v"(stab_o));
-      const int sT = slot_start(k, wave_o, NT), sU = slot_start(k + 1, wave_o, NT);
-      const unsigned mT = (1u << sU) - (1u << sT);  // this wave's tiles (k, b), b > k
-      const bool own = wave_o == k % NW;
-      if (mT != 0u || own) {
-        const double* LT = DT + k * DTS;
-        double la[4], zk[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          la[r] = LT[(4 * r + (lane_o >> 4)) * LIS + (lane_o & 15)];  // L^-1[l&15][4r+(l>>4)]
-          zk[r] = ZP[k * 256 + r * 64 + lane_o];
-        }
-        d4 y = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) y = __builtin_amdgcn_mfma_f64_16x16x4f64(la[r], zk[r], y, 0, 0, 0);
-        if (own) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) gram = __builtin_amdgcn_mfma_f64_16x16x4f64(y[r], y[r], gram, 0, 0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-          if ((mT >> s) & 1u) {
-            double* zb = ZP + (slot_ij(stab_o, s) & 0xffff) * 256 + lane_o;
-            d4 t;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = zb[64 * r];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[s][r], y[r], t, 0, 0, MFMA_NEG_A);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) zb[64 * r] = t[r];
-          }
-        }
-      }
-      __syncthreads();  // Z_{k+1} complete; nobody reads Z_k again
-    }
+    fwd_sweep_panel<SLOTS, false>(NT, DT, ZP, acc, wave, lane, stab, gram);
     // the waves' Gram parts, summed in wave order into block 0 of the (dead) panel
     for (int w = 0; w < NW; ++w) {
       if (wave == w) {
@@ -2447,6 +2480,8 @@ __global__ void k_build_cc(int P, int M, int n, int p, int NT, int has_prior, in
   }
 }
 
+#include "mhe_general.h"
+
 // ================================================================ host side
 // Shared by the translation units: model tables, path selection, and the launch
 // templates each pair_*.hip instantiates for its (dynamics, measurement) pairs.
@@ -2495,9 +2530,24 @@ inline int smem_bytes(const mhe_dims* dm, int NT, bool bounded = false, bool sb 
 // when they do not fit (e.g. autonomous-car.py: 231 rows x 9 x 9) the problem takes
 // the large-system path, which groups rows by epoch.
 constexpr int REG_LDS_LIMIT = 160 * 1024;
+static_assert(FG_LDS_DOUBLES * (int)sizeof(double) == REG_LDS_LIMIT, "k_gn_general sizes its LDS by the same limit");
+
+// Fused-general dims (mhe_dims.force_large == MHE_PATH_FUSED_GENERAL): a mixed-row problem
+// (with or without extra variables and equality rows) that k_gn_general takes in one launch --
+// L2 dynamics cost, no bounds, n <= 16, the node-major padded system within MAX_NT tiles and
+// the kernel's LDS layout (fg_smem_layout, at least one epoch) within REG_LDS_LIMIT.  A
+// function of dims alone; for every other dims the value 2 is the value 0.
+inline bool fg_eligible(const mhe_dims* dm) {
+  if (dm->force_large != MHE_PATH_FUSED_GENERAL || dm->meas_model != MHE_MEAS_MIXED) return false;
+  if (dm->dyn_cost != MHE_COST_L2 || dm->n_bounds != 0 || dm->n > 16) return false;
+  const int NT = ((dm->N + 1) * dm->n + 15) / 16;
+  if (NT > MAX_NT) return false;
+  return fg_epoch_cap(dm->N + 1, dm->M > 0 ? dm->M : 1, dm->n, NT, dm->n_extra, dm->n_eq) >= 1;
+}
 
 inline bool is_big(const mhe_dims* dm) {
-  if (dm->force_large) return true;
+  if (dm->force_large != MHE_PATH_AUTO && dm->force_large != MHE_PATH_FUSED_GENERAL) return true;
+  if (fg_eligible(dm)) return false;
   if (dm->meas_model == MHE_MEAS_MIXED || dm->n_extra > 0 || dm->n_eq > 0) return true;
   const int NT = ((dm->N + 1) * dm->n + 15) / 16;
   if (NT > MAX_NT) return true;
@@ -2613,6 +2663,8 @@ struct PairOps {
   int (*resjac)(ResjacArgs& a, int batch, hipStream_t st);
   // kernel-level parity of the large-system path: one stage (BIG_STAGE_*) on the workspace
   int (*big_stage)(const mhe_dims* dm, BigArgs& A, int batch, int stage, hipStream_t st);
+  // fused-general dims (fg_eligible): the whole bordered solve in one launch (k_gn_general)
+  int (*gn_general)(const mhe_dims* dm, GnArgs& a, int batch, hipStream_t st);
 };
 
 // compute units of the device the launch stream belongs to (not the calling thread's
@@ -2710,12 +2762,33 @@ int launch_gn(const mhe_dims* dm, GnArgs& a, int batch, int mode, hipStream_t st
   }
 }
 
+// k_gn_general (mhe_general.h), the instance of the mixed pairs with n <= 16: one launch per
+// batch, one workgroup per trajectory.  MINW = 2: with 128 VGPRs (MINW = 4) every instance
+// spills (58 .. 405 VGPRs), and the LDS layout of the shapes this path is for (two-receiver
+// N = 10: 121 KB used) admits one workgroup per CU anyway.
+constexpr int FG_MINW = 2;
+template <class DYN, class MEAS>
+int launch_gn_general(const mhe_dims* dm, GnArgs& a, int batch, hipStream_t st) {
+  if constexpr (MEAS::MIXED && DYN::n <= 16) {
+    const int EC = fg_epoch_cap(a.P, a.M > 0 ? a.M : 1, DYN::n, a.NT, a.nz, a.nc);
+    const int smem = fg_smem_layout(a.P, a.M < EC ? a.M : EC, DYN::n, a.NT, a.nz, a.nc).total * (int)sizeof(double);
+    if (EC < 1 || smem > REG_LDS_LIMIT) return MHE_ERR_UNSUPPORTED;
+    void (*kern)(GnArgs) = k_gn_general<DYN, MEAS, MAX_SLOTS, FG_MINW>;
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
+      return MHE_ERR_HIP;
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(NTHREADS), smem, st, a);
+    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  } else {
+    return MHE_ERR_UNSUPPORTED;
+  }
+}
+
 template <class DYN, class MEAS>
 int launch_build_cc(const mhe_dims* dm, int NT, const double* D, const double* cw, const double* Phi,
                     const double* Qw, const double* Rw, const double* Pw, char* cbuf, hipStream_t st) {
-  if constexpr (MEAS::MIXED) {
+  if constexpr (MEAS::MIXED && DYN::n > 16) {
     return MHE_ERR_UNSUPPORTED;
-  } else {
+  } else {  // (mixed rows, n <= 16: the tile tables of k_gn_general -- no measurement term in Cc)
     const int ntiles = NT * (NT + 1) / 2;
     hipLaunchKernelGGL(k_build_cc<MEAS>, dim3((ntiles * 256 + 255) / 256), dim3(256), 0, st, dm->N + 1, dm->M,
                        dm->n, dm->p, NT, dm->has_prior, dm->dyn_cost == MHE_COST_HUBER ? 1 : 0, 2.0 / dm->T, D, cw,
@@ -2971,7 +3044,8 @@ int launch_big(const mhe_dims* dm, BigArgs& A, int batch, int max_iter, hipStrea
 template <class DYN, class MEAS>
 const PairOps* pair_ops() {
   static const PairOps ops = {&launch_build_cc<DYN, MEAS>, &launch_gn<DYN, MEAS>, &launch_big<DYN, MEAS>,
-                              &launch_resjac<DYN, MEAS>, &launch_big_stage<DYN, MEAS>};
+                              &launch_resjac<DYN, MEAS>, &launch_big_stage<DYN, MEAS>,
+                              &launch_gn_general<DYN, MEAS>};
   return &ops;
 }
 

@@ -157,6 +157,69 @@ __global__ void k_big_epoch_rows(int P, int M, int n, int p, const double* Phi, 
   }
 }
 
+// ------------------------------------------------------------ fused-general constants (mhe_general.h)
+// D, D^T, the weights and the equality rows (the tile tables come from k_build_cc)
+__global__ void k_fg_consts(int P, int M, int n, int NT, int nc, EqPairs eqp, const double* D, const double* cw,
+                            const double* Qw, const double* Rw, const double* Pw, char* cbuf) {
+  const FgConst FC = fg_const_layout(P, M, n, NT, nc);
+  const ConstLayout& CL = FC.C;
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  double* oD = (double*)(cbuf + CL.D);
+  double* oDt = (double*)(cbuf + CL.Dt);
+  for (int e = gid; e < P * P; e += stride) {
+    const int k = e / P, j = e % P;
+    oD[e] = D[e];
+    oDt[j * P + k] = D[e];
+  }
+  for (int e = gid; e < P; e += stride) ((double*)(cbuf + CL.cw))[e] = cw[e];
+  for (int e = gid; e < n * n; e += stride) {
+    ((double*)(cbuf + CL.Qw))[e] = Qw[e];
+    ((double*)(cbuf + CL.Pw))[e] = Pw ? Pw[e] : 0.0;
+  }
+  for (int e = gid; e < M; e += stride) ((double*)(cbuf + CL.Rw))[e] = Rw[e];
+  for (int e = gid; e < 2 * nc; e += stride) ((int*)(cbuf + FC.eq))[e] = eqp.v[e];
+  for (int e = gid; e < nc; e += stride) ((double*)(cbuf + FC.eqr))[e] = eqp.r[e];
+}
+
+// Epochs as the large path detects them (row i starts one unless its Phi row equals row
+// i - 1 bitwise), the epoch rows Phi_E / Phi_E^T and the row -> epoch map; one workgroup.
+__global__ void k_fg_epochs(int P, int M, int n, int NT, int nc, const double* Phi, char* cbuf) {
+  const FgConst FC = fg_const_layout(P, M, n, NT, nc);
+  int* flag = (int*)(cbuf + FC.flag);
+  int* erow = (int*)(cbuf + FC.erow);
+  int* rowe = (int*)(cbuf + FC.rowe);
+  double* PhiE = (double*)(cbuf + FC.C.Phi);
+  double* PhiET = (double*)(cbuf + FC.C.PhiT);
+  for (int i = threadIdx.x; i < M; i += blockDim.x) {
+    int f = (i == 0);
+    if (!f)
+      for (int j = 0; j < P; ++j)
+        if (__double_as_longlong(Phi[(size_t)i * P + j]) != __double_as_longlong(Phi[(size_t)(i - 1) * P + j])) {
+          f = 1;
+          break;
+        }
+    flag[i] = f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int E = 0;
+    for (int i = 0; i < M; ++i) {
+      if (flag[i]) erow[E++] = i;
+      rowe[i] = E - 1;
+    }
+    erow[E] = M;
+    *(int*)(cbuf + FC.ne) = E;
+  }
+  __syncthreads();
+  const int E = *(const int*)(cbuf + FC.ne);
+  for (int t = threadIdx.x; t < M * P; t += blockDim.x) {
+    const int e = t / P, j = t % P;
+    const double v = e < E ? Phi[(size_t)erow[e] * P + j] : 0.0;
+    PhiE[(size_t)e * P + j] = v;
+    PhiET[(size_t)j * M + e] = v;
+  }
+}
+
 __global__ void k_write_tag(unsigned long long* p, unsigned long long tag) { *p = tag; }
 
 int g_opt_big_right_looking = 0;
@@ -231,6 +294,7 @@ int check_dims(const mhe_dims* dm, int* NT_out) {
 // constants proper
 size_t const_total_bytes(const mhe_dims* dm, int NT) {
   if (is_big(dm)) return big_const_layout(dm->N + 1, dm->M, dm->n, dm->p, dm->n_eq).total;
+  if (fg_eligible(dm)) return fg_const_layout(dm->N + 1, dm->M, dm->n, NT, dm->n_eq).total;
   return const_layout(dm->N + 1, dm->M, dm->n, dm->p, NT).total;
 }
 
@@ -244,7 +308,8 @@ unsigned long long const_tag(const mhe_dims* dm, int NT) {
     h ^= (unsigned long long)x;
     h *= 1099511628211ull;
   };
-  const long long v[] = {0x4D4845, is_big(dm) ? 1 : 0, dm->N, dm->n, dm->m, dm->p, dm->M, dm->q, dm->dyn_model,
+  // the path bit: 0 register-resident, 1 large-system, 2 fused-general (k_gn_general's layout)
+  const long long v[] = {0x4D4845, is_big(dm) ? 1 : fg_eligible(dm) ? 2 : 0, dm->N, dm->n, dm->m, dm->p, dm->M, dm->q, dm->dyn_model,
                          dm->meas_model, dm->has_prior, dm->dyn_cost, NT, dm->n_eq, dm->n_extra};
   for (long long x : v) mix(x);
   if (dm->n_eq > 0 && dm->eq_idx)  // check_dims has validated n_eq <= MHE_MAX_EQ and eq_idx
@@ -303,7 +368,35 @@ GnArgs make_args(const mhe_dims* dm, const void* cbuf, int NT) {
     a.bub[i] = dm->bound_ub[i];
     a.dpar[i] = dm->dyn_par[i];
   }
+  a.nz = dm->n_extra;
+  a.nc = dm->n_eq;
   return a;
+}
+
+// Constants of fused-general dims (fg_const_layout): the register path's tables, the epoch-
+// compressed basis and the equality rows.  Phi with more distinct rows than the kernel's LDS
+// layout holds (fg_epoch_cap) is refused -- the one host synchronisation of this build.
+int build_fg_consts(const mhe_dims* dm, int NT, const PairOps* ops, const double* D, const double* cw,
+                    const double* Phi, const double* Qw, const double* Rw, const double* Pw, char* cbuf,
+                    hipStream_t st) {
+  const int P = dm->N + 1;
+  EqPairs e = {};
+  for (int i = 0; i < 2 * dm->n_eq; ++i) e.v[i] = dm->eq_idx[i];
+  for (int i = 0; i < dm->n_eq; ++i) e.r[i] = dm->eq_rhs ? dm->eq_rhs[i] : 0.0;
+  hipLaunchKernelGGL(k_fg_consts, dim3(64), dim3(256), 0, st, P, dm->M, dm->n, NT, dm->n_eq, e, D, cw, Qw, Rw, Pw,
+                     cbuf);
+  int rc = ops->build_cc(dm, NT, D, cw, Phi, Qw, Rw, Pw, cbuf, st);
+  if (rc != MHE_OK) return rc;
+  if (dm->M > 0) {
+    hipLaunchKernelGGL(k_fg_epochs, dim3(1), dim3(256), 0, st, P, dm->M, dm->n, NT, dm->n_eq, Phi, cbuf);
+    const FgConst FC = fg_const_layout(P, dm->M, dm->n, NT, dm->n_eq);
+    int E = 0;
+    if (hipMemcpyAsync(&E, cbuf + FC.ne, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return MHE_ERR_HIP;
+    if (E > fg_epoch_cap(P, dm->M, dm->n, NT, dm->n_extra, dm->n_eq)) return MHE_ERR_UNSUPPORTED;
+  }
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
 // The large-system path's launch arguments that follow from the dims and the
@@ -633,6 +726,8 @@ int mhe_build_constants(const mhe_dims* dims, const double* D, const double* cw,
   char* cb = (char*)const_buf;
   if (is_big(dims)) {
     rc = build_big_consts(dims, D, cw, Phi, Qw, Rw, Pw, cb, st);
+  } else if (fg_eligible(dims)) {
+    rc = build_fg_consts(dims, NT, ops, D, cw, Phi, Qw, Rw, Pw, cb, st);
   } else {
     hipLaunchKernelGGL(k_copy_consts, dim3(256), dim3(256), 0, st, dims->N + 1, dims->M, dims->n, dims->p, NT, D,
                        cw, Phi, Qw, Rw, Pw, cb);
@@ -693,6 +788,8 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  const bool fused = fg_eligible(dims);
+  if (fused && g->meas_delta) return MHE_ERR_UNSUPPORTED;  // k_gn_general has no robust rows
   if (is_big(dims)) {
     if (!g->workspace || g->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
     BigArgs A = make_big_args(dims, const_buf, NT, g->workspace);
@@ -719,6 +816,11 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   a.pstride = g->par_bstride; a.x0 = g->x0; a.cost = g->cost_out; a.iters = g->iters_out; a.status = g->status_out;
   a.max_iter = g->max_iter; a.tol = g->tol; a.Rw = g->Rw; a.rwstride = g->rw_bstride;
   a.md = g->meas_delta; a.mdstride = g->md_bstride; a.Pw = g->Pw; a.pwstride = g->pw_bstride;
+  if (fused) {
+    a.Z0 = g->Z0; a.Zout = g->Z_out;
+    a.lam = dims->n_eq > 0 ? g->lambda_out : nullptr;
+    return ops->gn_general(dims, a, batch, st);
+  }
   return ops->gn(dims, a, batch, MODE_SOLVE, st);
 }
 
@@ -826,6 +928,7 @@ int mhe_kkt_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_arg
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
+  if (fg_eligible(dims)) return MHE_ERR_UNSUPPORTED;  // k_gn_general solves only
   if (!is_general(dims))  // no border, typed rows: mhe_state_cov itself (both paths)
     return mhe_state_cov(dims, const_buf, at, PhiQ, n_query, cov_out, status_out, scratch, scratch_bytes, stream);
   if (!is_big(dims)) return MHE_ERR_UNSUPPORTED;  // every general problem takes the large-system path
@@ -870,6 +973,7 @@ int mhe_kkt_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
+  if (fg_eligible(dims)) return MHE_ERR_UNSUPPORTED;  // k_gn_general solves only
   // an equality row between state components makes the block rank-deficient: no inverse
   if (dims->n_eq > 0 || dims->n > ARR_NMAX) return MHE_ERR_UNSUPPORTED;
   if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_arrival
@@ -977,6 +1081,11 @@ int32_t mhe_solve_kernel_name(const mhe_dims* dims, int32_t batch, void* stream,
              dims->n_bounds > 0 ? "linesearch" : "update");
     return MHE_OK;
   }
+  if (fg_eligible(dims)) {
+    snprintf(buf, len, "k_gn_general<dyn %d, meas %d, SLOTS=%d, MINW=%d> (fused bordered solve, NT %d, K %d)",
+             dims->dyn_model, dims->meas_model, MAX_SLOTS, FG_MINW, NT, dims->n_extra + dims->n_eq);
+    return MHE_OK;
+  }
   const GnChoice c = gn_choice(dims, NT, batch, MODE_SOLVE, (hipStream_t)stream);  // a call without meas_delta
   if (c.smem > REG_LDS_LIMIT) return MHE_ERR_UNSUPPORTED;
   snprintf(buf, len, "mhe::%s<dyn %d, meas %d, SLOTS=%d, MODE_SOLVE, HUBER=%d%s>%s", c.bounded ? "k_gn_bounded" : "k_gn",
@@ -1082,6 +1191,7 @@ int mhe_chol_solve_ws(const mhe_dims* dims, const void* const_buf, int32_t batch
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
+  if (fg_eligible(dims)) return MHE_ERR_UNSUPPORTED;  // k_gn_general solves only
   if (!is_big(dims)) return mhe_chol_solve(dims, const_buf, batch, H, g, delta, status, stream);
   if (batch <= 0) return batch == 0 ? MHE_OK : MHE_ERR_DIMS;
   if (!const_buf || !H || !g || !delta || !status) return MHE_ERR_NULL;

@@ -15,6 +15,9 @@ MHE_OK = 0
 ERRORS = {-1: "MHE_ERR_DIMS", -2: "MHE_ERR_MODEL", -3: "MHE_ERR_HIP", -4: "MHE_ERR_UNSUPPORTED", -5: "MHE_ERR_NULL"}
 STATUS = {0: "converged", 1: "max_iter", 2: "not_spd", 3: "nonfinite", 4: "bad_constants"}
 OPT_BIG_RIGHT_LOOKING, OPT_DEBUG_SMEM_PAD = 1, 2  # mhe_set_option (A/B runs and tests only)
+# mhe_dims.force_large (MHE_PATH_*): 2 prefers the fused single-launch kernel for a mixed-row /
+# bordered problem that fits it (k_gn_general); for every other dims it is 0
+PATH_AUTO, PATH_LARGE, PATH_FUSED_GENERAL = 0, 1, 2
 
 # symbol -> (restype, argtypes); must match include/mhe.h exactly
 c_i32, c_i64, c_dbl, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t

@@ -79,6 +79,14 @@ class BatchSolver:
       eq_rhs          (K,) the constants r (None: 0, the addEqConstraint rows)
       force_large     take the large-system path even when the register-resident kernel
                       fits (parity tests of the two paths; fixed at construction)
+      fused_general   prefer the fused single-launch kernel (k_gn_general) for a mixed-row
+                      problem that fits it (L2 dynamics cost, no bounds, n <= 16, padded system
+                      <= 208; mhe.h MHE_PATH_FUSED_GENERAL) -- ``self.fused_general`` tells
+                      whether it does; otherwise the default path, bitwise.  Exclusive with
+                      force_large.  covariance / arrival / assemble / chol_solve and
+                      solve(meas_delta=) go through a default-path sibling (``sibling()``):
+                      their outputs are exactly the default path's (assemble / chol_solve
+                      exchange ITS padded KKT system, ``sibling().kkt_dim`` rows)
       dyn_par         static dynamics parameters (mhe_dims.dyn_par; registry.dyn_params turns a
                       plug-in's params dict into it, e.g. car_params for vehicle_dynamics_and_gnss)
       constants       "build" (default): build the device constants here; "receive": only
@@ -92,7 +100,9 @@ class BatchSolver:
 
     def __init__(self, N, T, dyn, meas, D, cw, Phi, Qw, Rw, Pw=None, meas_idx=None, device="cuda",
                  dyn_cost="l2", huber_delta=None, bounds=None, n_extra=0, eq=None, force_large=False,
-                 dyn_par=None, eq_rhs=None, constants="build"):
+                 dyn_par=None, eq_rhs=None, constants="build", fused_general=False):
+        if fused_general and force_large:
+            raise ValueError("fused_general and force_large are exclusive (one path preference per solver)")
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.MheLibraryError("no HIP device visible: the estimator has no CPU path")
@@ -144,7 +154,8 @@ class BatchSolver:
             dims.eq_rhs = self._eq_rhs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         self.n_eq = dims.n_eq
         self.lam = None
-        dims.force_large = 1 if force_large else 0
+        dims.force_large = (_lib.PATH_FUSED_GENERAL if fused_general else
+                            _lib.PATH_LARGE if force_large else _lib.PATH_AUTO)
         if dyn_par is None and dname == "vehicle_dynamics_and_gnss":
             raise ValueError("vehicle_dynamics_and_gnss needs dyn_par (registry.dyn_params(name, params))")
         dp = np.zeros(8) if dyn_par is None else np.asarray(dyn_par, dtype=np.float64).ravel()
@@ -152,14 +163,22 @@ class BatchSolver:
             dims.dyn_par[i] = float(dp[i]) if i < dp.size else 0.0
         self.dyn_par = dp
         self.dims = dims
-        self.dp = self.lib.mhe_padded_dim(dims)
-        if self.dp < 0:
-            raise _lib.MheCallError("mhe_padded_dim: unsupported dims (system too large for this build?)")
-        nbytes = self.lib.mhe_const_bytes(dims)
-        if nbytes == 0:
-            raise _lib.MheCallError("mhe_const_bytes: invalid dims")
+        # the fused single-launch kernel takes these dims (a preference: for every other dims
+        # fused_general=True is the default path): a general problem without a workspace
+        self.fused_general = bool(fused_general) and self.general and self.lib.mhe_workspace_bytes(dims, 1) == 0
+        self._sibling = None
+        self._ctor = None
+        if self.fused_general:
+            # host copies for the default-path sibling (covariance, arrival, assemble,
+            # chol_solve, robust rows), built on first use
+            host = lambda x: None if x is None else np.array(x.cpu() if isinstance(x, torch.Tensor) else x,  # noqa: E731
+                                                             dtype=np.float64)
+            self._ctor = dict(N=N, T=T, dyn=dyn, meas=meas, D=host(D), cw=host(cw), Phi=host(Phi), Qw=host(Qw),
+                              Rw=host(Rw), Pw=host(Pw), meas_idx=meas_idx, device=device, dyn_cost=dyn_cost,
+                              huber_delta=huber_delta, bounds=bounds, n_extra=n_extra, eq=eq, dyn_par=dyn_par,
+                              eq_rhs=eq_rhs)
+        self._alloc_constants()
         dev = self.device
-        self.cbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._ws = collections.OrderedDict()  # large-system workspace per stream handle (LRU, <= WS_CACHE)
         self._built = torch.cuda.Event()  # launches on any stream wait for the constants
         if constants == "receive":
@@ -175,13 +194,42 @@ class BatchSolver:
                    Pw=None if Pw is None else np.asarray(Pw, np.float64))
         src = {k: _dev(v, dev) for k, v in src.items() if v is not None}
         cur = torch.cuda.current_stream(dev)
-        rc = self.lib.mhe_build_constants(
+        build = lambda: self.lib.mhe_build_constants(  # noqa: E731
             self.dims, _ptr(src["D"]), _ptr(src["cw"]), _ptr(src["Phi"]),
             _ptr(src["Qw"]), _ptr(src["Rw"]), _ptr(src.get("Pw")), _ptr(self.cbuf), _handle(cur))
+        rc = build()
+        if rc == -4 and self.fused_general:
+            # more distinct measurement times than the fused kernel's LDS layout holds: the
+            # preference falls back to the default path
+            self.dims.force_large = _lib.PATH_AUTO
+            self.fused_general, self._ctor = False, None
+            self._alloc_constants()
+            rc = build()
         _lib.check(rc, "mhe_build_constants")
         # the staging tensors may be freed now: the build reads them on `cur`, where the
         # caching allocator orders their reuse
         self._built.record(cur)
+
+    def _alloc_constants(self):
+        self.dp = self.lib.mhe_padded_dim(self.dims)
+        if self.dp < 0:
+            raise _lib.MheCallError("mhe_padded_dim: unsupported dims (system too large for this build?)")
+        nbytes = self.lib.mhe_const_bytes(self.dims)
+        if nbytes == 0:
+            raise _lib.MheCallError("mhe_const_bytes: invalid dims")
+        self.cbuf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def sibling(self):
+        """The default-path solver of the same problem, for what the fused kernel does not do
+        (covariance, arrival, assemble, chol_solve, solve with meas_delta): built on first use
+        from the host arrays this solver keeps; outputs and refusals are the default path's."""
+        if not self.fused_general:
+            raise _lib.MheCallError("sibling(): not a fused-general solver")
+        if self._sibling is None:
+            if self._ctor["D"] is None:
+                raise _lib.MheCallError("sibling(): this solver received its constants and has no host arrays")
+            self._sibling = BatchSolver(**self._ctor)
+        return self._sibling
 
     def constants_ready(self, stream=None):
         """A solver built with constants="receive": self.cbuf now holds the bytes another
@@ -403,8 +451,14 @@ class BatchSolver:
         that stream; consume the outputs there or make the consuming stream wait for it.
         ``lam_out`` (B, n_eq) float64 device tensor: receives this solve's constraint
         multipliers (the per-call way; ``self.lam`` is the last solve's on any stream,
-        kept for single-stream callers)."""
+        kept for single-stream callers).  A fused-general solver runs k_gn_general; with
+        ``meas_delta`` its default-path sibling does."""
         self._check_ready()
+        if self.fused_general and meas_delta is not None:
+            sib = self.sibling()
+            r = sib.solve(X0, U, Y, PAR, x0, max_iter, tol, stream, out, Z0, Rw, lam_out, meas_delta, Pw)
+            self.lam = sib.lam
+            return r
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
             X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X0, U, Y, PAR, x0)
             if out is None:
@@ -482,6 +536,8 @@ class BatchSolver:
         weights at X and the robust cost).  ``status_out``: also return the
         per-trajectory status (0, or 4 = constants built for other dims)."""
         self._check_ready()
+        if self.fused_general:
+            return self.sibling().assemble(X, U, Y, PAR, x0, stream, status_out, Z, Rw, meas_delta, Pw)
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
             X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
             Z_t = None
@@ -567,6 +623,8 @@ class BatchSolver:
         solve's (B, n_extra)) goes through mhe_kkt_arrival; with equality rows the block is
         rank-deficient and the call is refused (MHE_ERR_UNSUPPORTED)."""
         self._check_ready()
+        if self.fused_general:
+            return self.sibling().arrival(X, U, Y, PAR, x0, t, Phi, Rw, meas_delta, Pw, stream, with_cov, Z)
         Phi = self._query_rows(t, Phi)
         if Phi.shape[0] != 1:
             raise ValueError(f"arrival() takes exactly one query time, got {Phi.shape[0]}")
@@ -631,6 +689,8 @@ class BatchSolver:
         row depends on; None without extra variables).  A typed solver makes the mhe_state_cov
         call whatever these two arguments are."""
         self._check_ready()
+        if self.fused_general:
+            return self.sibling().covariance(X, U, Y, PAR, x0, t, Phi, Rw, stream, meas_delta, Pw, Z, with_extra)
         Phi = self._query_rows(t, Phi)
         Tq = Phi.shape[0]
         if Tq == 0:
@@ -689,6 +749,8 @@ class BatchSolver:
         A bordered problem takes the KKT system of kkt_dim rows (``assemble``'s) and
         returns delta = [dx; dz; lambda], solved as every bordered GN step (k_big_border)."""
         self._check_ready()
+        if self.fused_general:
+            return self.sibling().chol_solve(H, g, stream)
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
             H = _dev(H, self.device)
             g = _dev(g, self.device)

@@ -243,6 +243,9 @@ class fixedTimeOptimalEstimationNLP(NLP):
         self._engine_key = None
         self.max_iter = 50
         self.tol = 1e-10
+        # prefer the fused single-launch kernel for a mixed-row problem that fits it
+        # (BatchSolver(fused_general=True)); set before build()
+        self.fused_general = False
 
     # ------------------------------------------------------------ recording
     def addVariables(self, N_var, n_var, lb=None, ub=None, name='x'):
@@ -628,12 +631,14 @@ class fixedTimeOptimalEstimationNLP(NLP):
         linear = registry.MEAS[mname][3]
         key = (mname, t_meas.tobytes(), Rw.tobytes() if linear else Rw.shape, None if Pw is None else Pw.tobytes(),
                self._dyn_cost.tobytes(), huber, tuple(bounds), nz, None if eq is None else eq.tobytes(),
-               None if eq_rhs is None else eq_rhs.tobytes(), None if dyn_par is None else dyn_par.tobytes())
+               None if eq_rhs is None else eq_rhs.tobytes(), None if dyn_par is None else dyn_par.tobytes(),
+               bool(self.fused_general))
         if self._engine is None or self._engine_key != key:
             self._engine = _solver.BatchSolver(self.N, self.T, func, mname, self.CPM.D, (self.T / 2.0) * self.CPM.w,
                                                Phi, self._dyn_cost, Rw, Pw=Pw, meas_idx=idx, device=self.device,
                                                dyn_cost="huber" if huber is not None else "l2", huber_delta=huber,
-                                               bounds=bounds, n_extra=nz, eq=eq, eq_rhs=eq_rhs, dyn_par=dyn_par)
+                                               bounds=bounds, n_extra=nz, eq=eq, eq_rhs=eq_rhs, dyn_par=dyn_par,
+                                               fused_general=bool(self.fused_general))
             self._engine_key = key
             self.engine_builds = getattr(self, "engine_builds", 0) + 1
         self._Rw_solve = None if linear else Rw

@@ -317,8 +317,13 @@ __device__ __forceinline__ double wave_max(double v) {
 }
 
 // block-wide reduction of up to 2 values (sum or max), result broadcast
+// SW: the wave index as a scalar (a per-lane copy is hoisted out of the caller's loop and
+// stays live in a VGPR across it)
+template <bool SW = false>
 __device__ __forceinline__ void block_reduce2(double* red, double& a, double& b, bool is_max) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  int wave = threadIdx.x >> 6;
+  if constexpr (SW) wave = __builtin_amdgcn_readfirstlane(wave);
   a = is_max ? wave_max(a) : wave_sum(a);
   b = is_max ? wave_max(b) : wave_sum(b);
   if (lane == 0) {
@@ -681,7 +686,12 @@ __device__ __forceinline__ double upper_half(double v) {
 // node_phase + meas_phase.  When both row counts fit one pass (P, M <= 128 with
 // 4 lanes per row: C1, C2) each lane runs its D-row and Phi-row dots together,
 // 16 L2 loads in flight instead of 8, halving the dependent round trips.
-template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false>
+// SKIP: a wave whose 16 rows all lie beyond P and M leaves at once (at P = M = 101 wave 7
+// would run the whole load, FMA and reduction stream on clamped rows and discard it).  The
+// reductions stay inside a wave and the phase has no barrier, so the exit is safe; the lane
+// to row mapping and the parts per row, hence every sum's order, are unchanged.  Enabled per
+// instance: the phases sit at the register-allocation edge.
+template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false, bool SKIP = false>
 __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL,
                                                   double* sm, int b, DIAG_FDECL, double* nzp = nullptr) {
   constexpr int n = DYN::n;
@@ -694,6 +704,8 @@ __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLa
   // lane % 16): the 4 lanes of a quad read 4 consecutive rows of D^T / Phi^T, one
   // 32-B piece of one line (with the parts in a quad they touched 4 lines)
   const int tid = opaque_tid();
+  if constexpr (SKIP)
+    if (16 * __builtin_amdgcn_readfirstlane(tid >> 6) >= (a.P > a.M ? a.P : a.M)) return 0.0;
   const int part = (tid >> 4) & 3, r = (tid >> 6) * 16 + (tid & 15);
   const int kk = r < a.P ? r : a.P - 1, ii = r < a.M ? r : a.M - 1;
   double dx[n], xi[n];
@@ -753,18 +765,37 @@ __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLa
   return cost;
 }
 
-template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false>
+template <class DYN, class MEAS, bool HUBER = false, bool NOISE = false, bool MHUBER = false, bool SKIP = false>
 __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL,
                                                   double* sm, int b, double* nzp = nullptr) {
   DIAG_DECL
-  return node_meas_phase<DYN, MEAS, HUBER, NOISE, MHUBER>(a, CL, SL, sm, b, DIAG_FARGS, nzp);
+  return node_meas_phase<DYN, MEAS, HUBER, NOISE, MHUBER, SKIP>(a, CL, SL, sm, b, DIAG_FARGS, nzp);
+}
+
+// prior cost (X_0 - x0)^T Pw (X_0 - x0), same operation order as grad_phase: the only cost
+// grad_phase adds (on the thread that owns node 0), for a pass that needs no gradient
+template <int n>
+__device__ __forceinline__ double prior_cost(const GnArgs& a, const double* Pw, const double* Xs, int b) {
+  double r0[n], cost = 0.0;
+#pragma unroll
+  for (int c = 0; c < n; ++c) r0[c] = Xs[c] - a.x0[(long long)b * n + c];
+#pragma unroll
+  for (int r = 0; r < n; ++r) {
+    double t2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < n; ++c) t2 += Pw[r * n + c] * r0[c];
+    cost += r0[r] * t2;
+  }
+  return cost;
 }
 
 // Gradient g = J^T W r (nlp/nlp.py:242-286 objective); writes BV = -g (padding 0).
 //   g_j = a sum_k D_kj V_k - F_j^T V_j - sum_i Phi_ij GE_i (+ Pw (X_0 - x0) at j = 0)
 // TPR lanes per node: half sum the D column, half the Phi column.
 // PW: the instance reads the per-solve prior weight a.Pw (prior_weight); false: the constants' only
-template <class DYN, bool PW = true>
+// SKIP: a wave whose 16 nodes are all padding (j0 + 16 wave >= P) goes straight to the
+// trailing zero fill -- see node_meas_phase
+template <class DYN, bool PW = true, bool SKIP = false>
 __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm, int b) {
   constexpr int n = DYN::n;
   const __amdgpu_buffer_rsrc_t rs = cbuf_rsrc(a.cbuf, CL.total);
@@ -784,6 +815,8 @@ __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout&
   const int q = (tid >> 4) & 3, sub = q % HP;
   const bool phi = q >= HP;
   for (int j0 = 0; j0 < a.P; j0 += NTHREADS / TPR) {
+    if constexpr (SKIP)
+      if (j0 + 16 * __builtin_amdgcn_readfirstlane(tid >> 6) >= a.P) break;  // wave-uniform; no barrier in the loop
     const int j = j0 + (tid >> 6) * 16 + (tid & 15);
     const int jj = j < a.P ? j : a.P - 1;
     const double* vec = phi ? GE : Vs;
@@ -2058,10 +2091,19 @@ __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL,
 // PW: a.Pw (the per-solve prior weight) is read, through a wave-uniform branch.  false: the
 // instance a plain MODE_SOLVE without Pw runs -- the parent's code (with the branch the C2
 // instance gained 12 B of scratch: profiles/arrival_resource_usage.txt)
+// TRIM (the MODE_SOLVE instances of the n = 2, linear-measurement, L2 problems: C2's shape):
+//   - the pass after the last step, whichever way the loop ends, forms the cost only: no
+//     gradient mat-vecs and BV stores that nothing reads (of grad_phase's cost just the prior
+//     term, prior_cost; the cost sum is bitwise the loop's);
+//   - waves whose rows are all padding leave the mat-vec phases at once (SKIP);
+//   - block_reduce2 holds the wave index in an SGPR.
+// The other instances keep the parent's code: with these changes everywhere the allocator
+// moved spills in 86 instances of the library, up in 35 (profiles/trim_resource_usage.txt).
 template <class DYN, class MEAS, int SLOTS, int mode, bool HUBER = false, int MINW = MHE_GN_MINW, bool SB = false,
           bool MHUBER = false, bool PW = true>
 __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   constexpr int n = DYN::n;
+  constexpr bool TRIM = mode == MODE_SOLVE && n == 2 && MEAS::LINEAR && !HUBER;
   static_assert(!SB || (mode == MODE_SOLVE && MINW <= 2 && NW == 8), "small-batch factorization: one workgroup per CU");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const ConstLayout CL = const_layout(a.P, a.M, n, MEAS::p, a.NT);
@@ -2113,13 +2155,16 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   int it = 0;
   DIAG_DECL
   for (;;) {
+    if constexpr (TRIM)
+      if (it >= a.max_iter) break;  // to the cost-only pass
     DIAG_MARK(7);
-    double c1 = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER>(FA, FCL, FSL, sm, opaque_s(b), DIAG_FARGS);
+    [[maybe_unused]] double c1 =
+        node_meas_phase<DYN, MEAS, HUBER, false, MHUBER, TRIM>(FA, FCL, FSL, sm, opaque_s(b), DIAG_FARGS);
     DIAG_MARK(6);
     __syncthreads();
     DIAG_MARK(0);
-    c1 += grad_phase<DYN, PW>(FA, FCL, FSL, sm, opaque_s(b));
-    {
+    c1 += grad_phase<DYN, PW, TRIM>(FA, FCL, FSL, sm, opaque_s(b));
+    if constexpr (!TRIM) {
       // park this wave's part of the cost in LDS (a live register across the
       // factorization would spill): read back if the loop exits at this iterate
       const double cwv = wave_sum(c1);
@@ -2169,7 +2214,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       }
       return;
     }
-    if (it >= a.max_iter) break;
+    if constexpr (!TRIM)
+      if (it >= a.max_iter) break;
     build_tiles<DYN, MEAS, SLOTS, HUBER, false, PW>(FA, FCL, FSL, sm, acc, wave, lane, stab);
     DIAG_MARK(15);
     __syncthreads();
@@ -2198,7 +2244,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       dmax = isfinite(dv) ? fmax(dmax, fabs(dv)) : INFINITY;
       xmax = fmax(xmax, fabs(Xs[t] + dv));
     }
-    block_reduce2(RED, dmax, xmax, true);
+    block_reduce2<TRIM>(RED, dmax, xmax, true);
     if (dmax == INFINITY) {
       status = MHE_STATUS_NONFINITE;
       break;
@@ -2208,6 +2254,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     ++it;
     if (dmax <= a.tol * (1.0 + xmax)) {
       status = MHE_STATUS_CONVERGED;
+      if constexpr (TRIM) break;
       // final cost at the converged iterate
       double cf = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER>(FA, FCL, FSL, sm, opaque_s(b));
       __syncthreads();
@@ -2218,7 +2265,17 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
       goto done;
     }
   }
-  {
+  if constexpr (TRIM) {
+    // Cost at the returned iterate, whichever way the loop ended (a non-SPD pivot and a
+    // non-finite step leave Xs untouched).  block_reduce2 sums the waves' parts in the
+    // order of the parked sum below.
+    double cf = node_meas_phase<DYN, MEAS, HUBER, false, MHUBER, TRIM>(FA, FCL, FSL, sm, opaque_s(b));
+    if (threadIdx.x == 0 && a.has_prior)
+      cf += prior_cost<n>(a, PW ? prior_weight(a, FCL, b) : (const double*)(a.cbuf + FCL.Pw), Xs, b);
+    double z = 0.0;
+    block_reduce2<true>(RED, cf, z, false);
+    if (threadIdx.x == 0) a.cost[b] = cf;
+  } else {
     // every other exit (max_iter, non-SPD pivot, non-finite step) leaves Xs at the
     // iterate of the loop's last residual pass: its cost is already summed
     __syncthreads();
@@ -2264,22 +2321,6 @@ __device__ __forceinline__ void comp_box(const GnArgs& a, int c, double& lo, dou
       lo = fmax(lo, a.blb[i]);
       hi = fmin(hi, a.bub[i]);
     }
-}
-
-// prior cost (X_0 - x0)^T Pw (X_0 - x0), same operation order as grad_phase
-template <int n>
-__device__ __forceinline__ double prior_cost(const GnArgs& a, const double* Pw, const double* Xs, int b) {
-  double r0[n], cost = 0.0;
-#pragma unroll
-  for (int c = 0; c < n; ++c) r0[c] = Xs[c] - a.x0[(long long)b * n + c];
-#pragma unroll
-  for (int r = 0; r < n; ++r) {
-    double t2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < n; ++c) t2 += Pw[r * n + c] * r0[c];
-    cost += r0[r] * t2;
-  }
-  return cost;
 }
 
 #define FSLB smem_layout(opaque_s(a.P), opaque_s(a.M), n, opaque_s(a.NT), !MEAS::LINEAR, true)

@@ -369,6 +369,166 @@ __device__ __forceinline__ int slot_start(int j, int wave, int NT) {
   return base > wave ? (base - wave + NW - 1) / NW : 0;
 }
 
+// Panel-aware static tile ownership of factor_forward (the CHAIN instances of k_gn): which
+// wave holds tile (I, J) -- block row J of U, I > J -- in which slot, computed once per NT at
+// compile time so that one wave, wave 0, can run every panel with little else to do.
+//   row spread   a wave owns at most ceil((NT-1-J) / NW) tiles of row J (T(J) stays spread)
+//   slot limit   at most MAX_SLOTS tiles per wave
+//   slot order   a wave's slots are sorted by row J, then I: the tiles of row k are one slot
+//                range, the trailing tiles (rows > k) a suffix, tile (k, k+1) the first of
+//                its owner's T(k) range
+//   light wave   wave 0 takes only the tiles the two limits force on it -- what the other
+//                waves' slots cannot hold, and one tile of a row with a multiple of NW tiles
+//                -- and takes them from the earliest rows: 2 2 2 1 1 of rows 0..4 at NT = 13
+//                (6 4 2 1 0 0 .. tiles in rows > k, where the cyclic map's panel wave holds
+//                8.25 6.9 5.6 4.5 3.5 2.6 ..), one tile of row 0 at NT = 9
+//   the others   every other tile, row by row, to the wave with the most free slots; within a
+//                row, which tile I a wave gets keeps the block columns spread (backward solve)
+//   panel wave   wave 0 at every step: no wave holds fewer tiles in the rows > k (the diagonal
+//                blocks live in LDS, so any wave can run any panel)
+struct ChainMap {
+  unsigned short ij[NW][MAX_SLOTS];  // I | J << 8 of slot s, 0xffff: empty
+  unsigned char pre[NW][16];         // the wave's tiles in rows < j (slot_start)
+  unsigned char rows[MAX_NT][NW];    // tiles of row J held by wave w
+};
+
+constexpr ChainMap make_chain_map(int NT) {
+  ChainMap m = {};
+  int rem[NW] = {}, nslot[NW] = {}, colc[MAX_NT][NW] = {};
+  for (int w = 0; w < NW; ++w) {
+    rem[w] = MAX_SLOTS;
+    for (int s = 0; s < MAX_SLOTS; ++s) m.ij[w][s] = 0xffff;
+  }
+  // the light wave: what the row spread forces, then what the slot limit forces
+  int need = NT * (NT - 1) / 2 - (NW - 1) * MAX_SLOTS;
+  for (int J = 0; J + 1 < NT; ++J) {
+    const int n = NT - 1 - J, cap = (n + NW - 1) / NW;
+    const int f = n - (NW - 1) * cap > 0 ? n - (NW - 1) * cap : 0;
+    m.rows[J][0] = (unsigned char)f;
+    need -= f;
+  }
+  for (int J = 0; J + 1 < NT && need > 0; ++J) {
+    const int n = NT - 1 - J, cap = (n + NW - 1) / NW;
+    while (need > 0 && m.rows[J][0] < cap) ++m.rows[J][0], --need;
+  }
+  for (int J = 0; J + 1 < NT; ++J) {
+    const int n = NT - 1 - J, cap = (n + NW - 1) / NW;
+    for (int t = m.rows[J][0]; t < n; ++t) {
+      int best = -1;
+      for (int w = 1; w < NW; ++w)
+        if (m.rows[J][w] < cap && rem[w] > 0 && (best < 0 || rem[w] > rem[best])) best = w;
+      if (best < 0) return m;  // cannot be placed: a tile stays unowned and chain_map_ok fails
+      ++m.rows[J][best];
+      --rem[best];
+    }
+  }
+  // which of a row's tiles I = J+1 .. a wave gets: the backward solve works through one block
+  // column I per step, so each goes to the wave (with tiles left to take in this row) that
+  // holds the fewest of column I, then the one with the most left to take -- the late rows
+  // first (few waves share them), the early rows, where every wave takes part, even it out
+  int owner[MAX_NT][MAX_NT] = {};
+  for (int J = NT - 2; J >= 0; --J) {
+    int q[NW] = {};
+    for (int w = 0; w < NW; ++w) q[w] = m.rows[J][w];
+    for (int I = NT - 1; I > J; --I) {
+      int best = -1;
+      for (int w = 0; w < NW; ++w)
+        if (q[w] > 0 && (best < 0 || colc[I][w] < colc[I][best] || (colc[I][w] == colc[I][best] && q[w] > q[best]))) best = w;
+      --q[best];
+      ++colc[I][best];
+      owner[J][I] = best;
+    }
+  }
+  for (int J = 0; J + 1 < NT; ++J)
+    for (int I = J + 1; I < NT; ++I) m.ij[owner[J][I]][nslot[owner[J][I]]++] = (unsigned short)(I | (J << 8));
+  for (int w = 0; w < NW; ++w) {
+    int cnt = 0;
+    for (int j = 0; j < 16; ++j) {
+      m.pre[w][j] = (unsigned char)cnt;
+      if (j < MAX_NT) cnt += m.rows[j][w];
+    }
+  }
+  return m;
+}
+
+// the map is built for 8 waves of MAX_SLOTS slots (the -DMHE_NW=16 A/B shape keeps the cyclic map)
+constexpr bool CHAIN_NW = NW == 8;
+struct ChainMaps {
+  ChainMap nt[MAX_NT + 1];
+};
+constexpr ChainMaps make_chain_maps() {
+  ChainMaps a = {};
+  for (int NT = 1; CHAIN_NW && NT <= MAX_NT; ++NT) a.nt[NT] = make_chain_map(NT);
+  return a;
+}
+
+// each tile owned once, slot limit, row spread, slots sorted by row (then I), the prefix
+// counts consistent with the slots, wave 0 the lightest in the rows > k at every step
+constexpr bool chain_map_ok(const ChainMap& m, int NT) {
+  int seen[MAX_NT][MAX_NT] = {};
+  for (int w = 0; w < NW; ++w) {
+    int last = -1, rowc[MAX_NT] = {};
+    bool ended = false;
+    for (int s = 0; s < MAX_SLOTS; ++s) {
+      const int v = m.ij[w][s];
+      if (v == 0xffff) {
+        ended = true;
+        continue;
+      }
+      const int I = v & 0xff, J = v >> 8;
+      if (ended || I <= J || I >= NT) return false;
+      if ((J << 8 | I) <= last) return false;
+      last = J << 8 | I;
+      ++seen[I][J];
+      ++rowc[J];
+    }
+    for (int J = 0; J + 1 < NT; ++J) {
+      if (rowc[J] > (NT - 1 - J + NW - 1) / NW || rowc[J] != m.rows[J][w]) return false;
+      if (m.pre[w][J + 1] - m.pre[w][J] != rowc[J]) return false;
+    }
+    if (m.pre[w][0] != 0) return false;
+  }
+  for (int I = 0; I < NT; ++I)
+    for (int J = 0; J < NT; ++J)
+      if (seen[I][J] != (I > J ? 1 : 0)) return false;
+  // wave 0 runs every panel: no wave has fewer tiles in the rows > k, at any step k
+  for (int k = 0; k + 1 < NT; ++k) {
+    for (int w = 1; w < NW; ++w) {
+      int t0 = 0, tw = 0;
+      for (int J = k + 1; J + 1 < NT; ++J) t0 += m.rows[J][0], tw += m.rows[J][w];
+      if (tw < t0) return false;
+    }
+  }
+  return true;
+}
+constexpr bool chain_maps_ok(const ChainMaps& a) {
+  for (int NT = 1; NT <= MAX_NT; ++NT)
+    if (!chain_map_ok(a.nt[NT], NT)) return false;
+  return true;
+}
+constexpr ChainMaps CHAIN_MAPS_H = make_chain_maps();
+static_assert(!CHAIN_NW || chain_maps_ok(CHAIN_MAPS_H),
+              "panel-aware slot map: tile ownership, slot limit, row spread or slot order");
+// (internal linkage: one 5 KB copy in each translation unit that includes this header, read only
+// by those that instantiate a CHAIN kernel)
+static __constant__ ChainMaps CHAIN_MAPS = CHAIN_MAPS_H;
+
+// make_slot_table for the panel-aware map.  Lanes CHL_PRE + j, past the slots, carry the
+// wave's prefix counts (its tiles in rows < j): one v_readlane away like a slot's coordinates,
+// and no register of their own across the factorization (packed into an SGPR pair they cost
+// the bench instance 7 VGPR spills).
+// NT <= MAX_NT as for every register-resident kernel: launch_gn's callers route larger systems
+// to the large-system path, and the slots themselves hold no more than MAX_NT block rows.
+constexpr int CHL_PRE = 16;
+__device__ __forceinline__ int make_slot_table_chain(int wave, int lane, int NT) {
+  const ChainMap& m = CHAIN_MAPS.nt[NT];
+  if (lane >= CHL_PRE + 16) return -1;
+  if (lane >= CHL_PRE) return m.pre[wave][lane - CHL_PRE];
+  if (lane >= MAX_SLOTS) return -1;
+  const int v = m.ij[wave][lane];
+  return v == 0xffff ? -1 : (v & 0xff) | ((v >> 8) << 16);
+}
+
 // Per wave and block row I (< 16): the bit mask of the wave's slots holding a tile
 // (I, J), written once per launch (the backward solve tests one bit per slot
 // instead of decoding every slot's coordinates at every block step).
@@ -1319,7 +1479,17 @@ __device__ __forceinline__ void block_fwd(const double* LT, const double* b, dou
 //         then runs panel(k+1) while the other waves do the remaining tiles
 //         (look-ahead: no separate panel phase).
 // Two workgroup barriers per block row.  Returns false on a bad pivot.
-template <int SLOTS>
+// CHAIN (the CHAIN instances of k_gn): work off the chain panel(k) -> T(k) -> diagonal block
+// k+1 -> panel(k+1), with every floating-point operation, its operands and its order kept.
+//   - the panel-aware slot map (make_slot_table_chain): the slot ranges come from the prefix
+//     count lanes of the slot table, and wave 0, which holds the fewest tiles in the rows > k at
+//     every step, runs every panel (the cyclic map's panel wave (k+1) % NW holds 36 trailing
+//     tiles per factorization at NT = 13, wave 0 holds 13);
+//   - DOFF: the diagonal blocks J > k+1 are updated by the other waves, block k+1+w by wave w
+//     (and on in steps of NW-1): none is left for the panel wave after its panel (in LDS any
+//     wave can update any block, one wave per block and step).  Not in the instance that reads
+//     a per-solve prior weight (PW), where it costs two more SGPR spills.
+template <int SLOTS, bool CHAIN = false, bool DOFF = false>
 __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout& SL, double* sm,
                                                d4 (&acc)[SLOTS], int wave, int lane, int stab, DIAG_FDECL) {
   double* BV = sm + SL.BV;
@@ -1339,8 +1509,16 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
     asm volatile("" : "+s"(wave_o));
     asm volatile("" : "+v"(stab_o));
     // ---- T(k): U_kb = L_kk^-1 A_kb for the tiles (k, b) of this wave, slots [sT, sU)
-    const int sT = slot_start(k < 0 ? 0 : k, wave_o, NT), sU = slot_start(k + 1, wave_o, NT);
-    const int nS = slot_start(NT - 1, wave_o, NT);
+    int sT, sU, nS;
+    if constexpr (CHAIN) {
+      sT = slot_ij(stab_o, CHL_PRE + (k < 0 ? 0 : k));
+      sU = slot_ij(stab_o, CHL_PRE + k + 1);
+      nS = slot_ij(stab_o, CHL_PRE + NT - 1);
+    } else {
+      sT = slot_start(k < 0 ? 0 : k, wave_o, NT);
+      sU = slot_start(k + 1, wave_o, NT);
+      nS = slot_start(NT - 1, wave_o, NT);
+    }
     // the slot ranges [sT, sU) and [sU, nS) as wave-uniform bit masks: one bit test
     // per unrolled slot instead of two compares and their combination
     const unsigned mT = (1u << sU) - (1u << sT), mU = (1u << nS) - (1u << sU);
@@ -1368,7 +1546,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
     __syncthreads();
     DIAG_MARK(9);
     // ---- U(k)
-    const int pw = (k + 1) % NW;  // panel wave of this step
+    const int pw = CHAIN ? 0 : (k + 1) % NW;  // panel wave of this step
     if (wave_o == pw) {
       // the panel is the serial critical path of the factorization: issue it ahead
       // of the co-resident waves (the other workgroup's and this one's MFMA work)
@@ -1426,8 +1604,16 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
       }
     }
     DIAG_MARK(13);
-    // remaining diagonal blocks J > k + 1 of this wave
-    for (int J = wave_o; J < NT; J += NW) {
+    // remaining diagonal blocks J > k + 1 of this wave: cyclic, J = wave, wave + NW, ..
+    int Jfirst = wave_o;
+    constexpr int Jstride = DOFF ? NW - 1 : NW;
+    if constexpr (DOFF) {
+      // the blocks k + 2 .. NT - 1 over the waves 1 .. NW - 1: wave w takes k + 1 + w and on
+      // in steps of NW - 1, the panel wave 0 none
+      static_assert(CHAIN, "wave 0 runs every panel in the panel-aware map only");
+      Jfirst = k + 1 + (wave_o ? wave_o : NT);
+    }
+    for (int J = Jfirst; J < NT; J += Jstride) {
       if (J <= k + 1 || k < 0 || KO(2)) continue;
       double* DTj = DT + J * DTS;
       d4 t;
@@ -2099,11 +2285,15 @@ __device__ __forceinline__ void cov_sweep(const GnArgs& a, const SmemLayout& SL,
 //   - block_reduce2 holds the wave index in an SGPR.
 // The other instances keep the parent's code: with these changes everywhere the allocator
 // moved spills in 86 instances of the library, up in 35 (profiles/trim_resource_usage.txt).
+// CHAIN (the TRIM instances with the two-workgroups-per-CU factorization): the panel-aware slot
+// map and factor_forward<.., CHAIN>; every other instance, and every other user of
+// make_slot_table / slot_start, keeps the cyclic map.
 template <class DYN, class MEAS, int SLOTS, int mode, bool HUBER = false, int MINW = MHE_GN_MINW, bool SB = false,
           bool MHUBER = false, bool PW = true>
 __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   constexpr int n = DYN::n;
   constexpr bool TRIM = mode == MODE_SOLVE && n == 2 && MEAS::LINEAR && !HUBER;
+  constexpr bool CHAIN = TRIM && !SB && CHAIN_NW;
   static_assert(!SB || (mode == MODE_SOLVE && MINW <= 2 && NW == 8), "small-batch factorization: one workgroup per CU");
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const ConstLayout CL = const_layout(a.P, a.M, n, MEAS::p, a.NT);
@@ -2111,7 +2301,9 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x;
-  const int stab = SB ? make_slot_table_sb(wave, lane, a.NT) : make_slot_table(wave, lane, a.NT);
+  const int stab = SB      ? make_slot_table_sb(wave, lane, a.NT)
+                   : CHAIN ? make_slot_table_chain(wave, lane, a.NT)
+                           : make_slot_table(wave, lane, a.NT);
   init_rowmask<SLOTS>((int*)(sm + SL.ROWM), wave, lane, stab);
   SbMasks sbm = {0u, 0u, 0u};
   if constexpr (SB) sbm = sb_masks<SLOTS>(lane, stab, a.NT);
@@ -2224,7 +2416,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     if constexpr (SB)
       ok = factor_forward_sb<SLOTS>(FA, FSL, sm, acc, wave, lane, stab, sbm, DIAG_FARGS);
     else
-      ok = factor_forward<SLOTS>(FA, FSL, sm, acc, wave, lane, stab, DIAG_FARGS);
+      ok = factor_forward<SLOTS, CHAIN, CHAIN && !PW>(FA, FSL, sm, acc, wave, lane, stab, DIAG_FARGS);
     DIAG_MARK(3);
     if (!ok) {
       status = MHE_STATUS_NOT_SPD;

@@ -119,6 +119,122 @@ def multi_receiver_problem(N=7, T=6.0, B=2, seed=1):
     return pb, X0, Z0, None, Y, np.tile(rows[None], (B, 1, 1)), xt, zt
 
 
+def spd(rng, diag, scale=0.2):
+    """diag(diag) plus a small random A A^T in diag's own scaling: a full SPD matrix."""
+    d = np.sqrt(np.asarray(diag, dtype=np.float64))
+    A = rng.normal(size=(d.size, d.size)) * scale / np.sqrt(d.size)
+    return np.diag(d) @ (np.eye(d.size) + A @ A.T) @ np.diag(d)
+
+
+def _rk4_nodes(f, x0, t, substeps=40):
+    """Fixed-step RK4 of x' = f(t, x) from x0 over the sample times t (one trajectory)."""
+    out = np.zeros((t.size, x0.size))
+    x = out[0] = x0
+    for i in range(1, t.size):
+        h, tt = (t[i] - t[i - 1]) / substeps, t[i - 1]
+        for _ in range(substeps):
+            k1 = f(tt, x)
+            k2 = f(tt + h / 2, x + h / 2 * k1)
+            k3 = f(tt + h / 2, x + h / 2 * k2)
+            k4 = f(tt + h, x + h * k3)
+            x = x + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
+            tt += h
+        out[i] = x
+    return out
+
+
+def _mixed_measurements(rng, rows, Phi, xt, sigma):
+    Y = np.zeros((xt.shape[0], len(rows), 1))
+    for b in range(xt.shape[0]):
+        for i in range(len(rows)):
+            Y[b, i, 0] = gg.mixed_row(rows[i], Phi[i] @ xt[b])[0] + rng.normal() * sigma[i]
+    return Y
+
+
+def kinematic_mixed_problem(N=6, T=5.0, B=4, seed=3, with_eq=False):
+    """rc-car-shaped problem on mixed rows: kinematic_bycicle_and_bias (n = 6, m = 2; x[2] is
+    the heading and the third pseudorange coordinate, as the reference has it), pseudoranges on
+    idx [0, 1, 2, 3] of 8 satellites at 6 epochs, a COMPONENT row on x[5] at 4 times (x[5]
+    enters no pseudorange and no other state's dynamics: without these rows and the prior the
+    problem is singular), full SPD Q and prior weight.  with_eq: the clock drift x[4] (constant
+    in the model) equal at the first and the last node, and x[2] equal at nodes 2 and 3."""
+    from oracle import models
+    rng = np.random.default_rng(seed)
+    n, m, P = 6, 2, N + 1
+    D, c = oc.diff_matrix(N), (T / 2.0) * oc.quad_weights(N)
+    t_nodes = oc.tau2t(oc.nodes(N), 0.0, T)
+    ctrl = lambda t: np.array([0.35 + 0.1 * np.sin(0.9 * t), 0.4 * np.sin(0.6 * t + 0.5)])  # noqa: E731
+    t_gnss, t_head = np.linspace(0, T, 6), np.linspace(0.5, T - 0.5, 4)
+    sats = rng.normal(size=(6, 8, 3)) * 1.5e7 + np.array([0, 0, 2e7])
+    rows, times, Rw, sigma = [], [], [], []
+    for i, t in enumerate(t_gnss):
+        for j in range(8):
+            rows.append(row(gg.ROW_PR, [0, 1, 2, 3], sats[i, j])); times.append(t); Rw.append(0.1); sigma.append(3.0)
+    for t in t_head:
+        rows.append(row(gg.ROW_COMP, [5])); times.append(t); Rw.append(25.0); sigma.append(0.2)
+    order = np.argsort(times, kind="stable")
+    rows, times, Rw, sigma = (np.array(v)[order] for v in (rows, times, Rw, sigma))
+    Phi = oc.interp_matrix(N, T, times)
+    xt = np.zeros((B, P, n))
+    for b in range(B):
+        x0 = np.concatenate([rng.normal(size=2) * 10.0, [rng.uniform(-1.0, 1.0), rng.normal() * 100.0,
+                                                         rng.normal() * 0.5, rng.uniform(-1.0, 1.0)]])
+        xt[b] = _rk4_nodes(lambda t, x: models.dyn_eval("kinematic_bycicle_and_bias", x, ctrl(t))[0], x0, t_nodes)
+    U = np.tile(np.stack([ctrl(t) for t in t_nodes])[None], (B, 1, 1))
+    Y = _mixed_measurements(rng, rows, Phi, xt, sigma)
+    Qw = np.linalg.inv(spd(rng, [1, 1, 0.01, 0.1, 0.1, 1]))
+    Pw = np.linalg.inv(spd(rng, [4, 4, 0.04, 4, 0.04, 0.04]))
+    eq = np.array([[4, N * n + 4], [2 * n + 2, 3 * n + 2]]) if with_eq else None
+    pb = gg.GeneralProblem(N, T, n, m, "kinematic_bycicle_and_bias", "mixed", D, c, Phi, Qw, Rw, Pw=Pw, eq=eq)
+    x0 = xt[:, 0] + rng.normal(size=(B, n)) * np.array([1.0, 1.0, 0.1, 1.0, 0.1, 0.1])
+    X0 = xt + rng.normal(size=(B, 1, n)) * np.array([2.0, 2.0, 0.05, 2.0, 0.05, 0.1])
+    return pb, X0, U, Y, np.tile(rows[None], (B, 1, 1)), x0, xt
+
+
+def vehicle_mixed_problem(N=5, T=2.0, B=4, seed=5, with_eq=False):
+    """autonomous-car-shaped problem on mixed rows: vehicle_dynamics_and_gnss (n = 9, m = 2,
+    car_params of tests/autocar.py), pseudoranges on idx [0, 1, 8, 6] of 8 satellites at 5
+    epochs, COMPONENT rows on the heading x[2] and the yaw rate x[5] at 4 times, full SPD Q and
+    prior weight; the forward speed stays near 8 m/s, far from the tyre model's pole at
+    vx = -0.001.  with_eq: the height x[8] (constant in the model) equal at the first and the
+    last node, and the clock drift x[7] equal at nodes 1 and 2."""
+    from oracle import models
+    from autocar import CAR
+    rng = np.random.default_rng(seed)
+    n, m, P = 9, 2, N + 1
+    D, c = oc.diff_matrix(N), (T / 2.0) * oc.quad_weights(N)
+    t_nodes = oc.tau2t(oc.nodes(N), 0.0, T)
+    ctrl = lambda t: np.array([1500.0 + 800.0 * np.sin(0.35 * t), 0.04 * np.sin(0.5 * t + 0.3)])  # noqa: E731
+    t_gnss, t_imu = np.linspace(0, T, 5), np.linspace(0.2, T - 0.2, 4)
+    sats = rng.normal(size=(5, 8, 3)) * 1.5e7 + np.array([0, 0, 2e7])
+    rows, times, Rw, sigma = [], [], [], []
+    for i, t in enumerate(t_gnss):
+        for j in range(8):
+            rows.append(row(gg.ROW_PR, [0, 1, 8, 6], sats[i, j])); times.append(t); Rw.append(0.1); sigma.append(3.0)
+    for t in t_imu:
+        rows.append(row(gg.ROW_COMP, [2])); times.append(t); Rw.append(400.0); sigma.append(0.05)
+        rows.append(row(gg.ROW_COMP, [5])); times.append(t); Rw.append(400.0); sigma.append(0.05)
+    order = np.argsort(times, kind="stable")
+    rows, times, Rw, sigma = (np.array(v)[order] for v in (rows, times, Rw, sigma))
+    Phi = oc.interp_matrix(N, T, times)
+    xt = np.zeros((B, P, n))
+    for b in range(B):
+        x0 = np.array([rng.normal() * 5.0, rng.normal() * 5.0, rng.uniform(-0.5, 0.5), 8.0 + rng.uniform(-1.0, 1.0),
+                       0.0, 0.0, 100.0 + rng.normal() * 10.0, 2.0 + rng.normal() * 0.2, rng.normal()])
+        xt[b] = _rk4_nodes(lambda t, x: models.dyn_eval("vehicle_dynamics_and_gnss", x, ctrl(t), CAR)[0], x0, t_nodes)
+    assert xt[:, :, 3].min() > 5.0
+    U = np.tile(np.stack([ctrl(t) for t in t_nodes])[None], (B, 1, 1))
+    Y = _mixed_measurements(rng, rows, Phi, xt, sigma)
+    Qw = np.linalg.inv(spd(rng, [0.1, 0.1, 0.01, 1, 1, 1, 0.1, 0.01, 0.01]))
+    Pw = np.linalg.inv(spd(rng, [4, 4, 0.04, 1, 1, 0.25, 4, 0.04, 1]))
+    eq = np.array([[8, N * n + 8], [1 * n + 7, 2 * n + 7]]) if with_eq else None
+    pb = gg.GeneralProblem(N, T, n, m, "vehicle_dynamics_and_gnss", "mixed", D, c, Phi, Qw, Rw, Pw=Pw, eq=eq,
+                           dyn_par=CAR)
+    x0 = xt[:, 0] + rng.normal(size=(B, n)) * np.array([1.0, 1.0, 0.1, 0.5, 0.5, 0.2, 1.0, 0.1, 0.5])
+    X0 = xt + rng.normal(size=(B, 1, n)) * np.array([2.0, 2.0, 0.05, 0.3, 0.1, 0.05, 2.0, 0.05, 0.5])
+    return pb, X0, U, Y, np.tile(rows[None], (B, 1, 1)), x0, xt
+
+
 # ---------------------------------------------------------------------------
 # gnss-multi-receiver.py (two receivers, 96 MHE windows) restated on the oracle
 TWO_RX = dict(T=5.0, N=10, n=10, m=6, r_pr_A=10.0, r_pr_B=1.0, r_range=0.01, r_heading=0.1,

@@ -650,7 +650,7 @@ typedef struct mhe_ekf_dims {
  * mu (B,n) and S (B,n,n) hold the prior on entry and the final state on exit;
  * mu_hist (B,steps,n) / S_hist (B,steps,n,n) (optional) receive the state after
  * every update; status (B, optional): 0 ok, 1 innovation covariance not SPD,
- * 2 nz > 32.  Returns MHE_OK or a negative MHE_ERR_*.
+ * 2 nz > pmax (the step is then predict-only).  Returns MHE_OK or a negative MHE_ERR_*.
  */
 int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* mu, double* S,
                 const double* U, int64_t u_bstride, const double* Z, int64_t z_bstride,

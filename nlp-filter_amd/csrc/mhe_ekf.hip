@@ -22,7 +22,7 @@
 namespace mhe_ekf {
 
 constexpr int NWF = 4;     // filters (waves) per workgroup
-constexpr int MAXP = 32;   // measurement rows per step (nz <= MAXP)
+constexpr int MAXP = 32;   // measurement rows per step (nz <= pmax <= MAXP; mhe_ekf_run checks pmax)
 
 // ---------------------------------------------------------------- plug-ins
 // gnss_pos_and_bias, utils/gnss.py:79-90: x+ = x + dt [u0, u1, u2, x4, 0],
@@ -252,7 +252,8 @@ __global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     const int nz = a.nz[(long long)b * a.nz_bstride + (long long)k * a.es];
-    if (nz > 0 && nz <= MAXP) {
+    // Z / PAR / R hold pmax (<= MAXP) rows per step: a step that claims more is refused
+    if (nz > 0 && nz <= a.nmeas_rows_max) {
       // ---- measurement rows at mu- (utils/ekf.py:51)
       const long long rk = (long long)k * a.nmeas_rows_max + lane;  // row index within the instance
       if (lane < nz) {
@@ -330,7 +331,7 @@ __global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
         mu[t] = MP[t] + acc;
       }
     } else {
-      if (nz > MAXP) status = 2;
+      if (nz > a.nmeas_rows_max) status = 2;
       for (int t = lane; t < n * n; t += 64) S[t] = SP[t];
       for (int t = lane; t < n; t += 64) mu[t] = MP[t];
     }
@@ -419,8 +420,9 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
     for (int c = 0; c < n; ++c) mu[c] = mp[c];
     // ---- correct: sequential scalar updates at the linearisation point mu-
     const int nz = a.nz[(long long)b * a.nz_bstride + (long long)k * a.es];
-    if (nz > MAXP) status = 2;
-    const int rows = nz <= MAXP ? nz : 0;
+    // Z / PAR / R hold pmax (<= MAXP) rows per step: a step that claims more is refused
+    if (nz > a.nmeas_rows_max) status = 2;
+    const int rows = nz <= a.nmeas_rows_max ? nz : 0;
     // with batch-innermost inputs (es = batch) consecutive lanes read consecutive words
     const double* zk = a.Z + (long long)b * a.z_bstride + (long long)k * a.nmeas_rows_max * a.es;
     const double* pk = a.PAR + (long long)b * a.par_bstride + (long long)k * a.nmeas_rows_max * q * a.es;

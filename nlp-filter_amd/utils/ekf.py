@@ -137,7 +137,9 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     (needed for discrete_vehicle_dynamics: "car_params"; its "dt", when given, wins
     over dt).  Inputs may be NumPy or torch.
     Returns (mu_hist (B,T,n), S_hist (B,T,n,n), mu (B,n), S (B,n,n), status (B))
-    as torch tensors on the device.
+    as torch tensors on the device.  status: 0 ok, 1 innovation covariance not
+    positive definite, 2 nz > pmax at some step (that step is predict-only; nz may be
+    a device tensor and is not checked on the host).
 
     method: "lane" (diagonal R: sequential scalar updates, one filter per lane),
     "wave" (any R: one wavefront per filter, augmented Cholesky sweep) or "auto"

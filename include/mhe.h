@@ -208,9 +208,13 @@ typedef struct mhe_dims {
  *                              slower); 0 (default): left-looking block columns
  *   MHE_OPT_DEBUG_SMEM_PAD     bytes of LDS added to the fused kernel's launch
  *                              (forces lower occupancy; default 0)
+ *   MHE_OPT_LSM_GROUP          16 or 64: mhe_ls_multi_run launches that lane-group
+ *                              instance whatever the row capacity; 0 (default): the
+ *                              row-capacity rule (mhe_ls_multi_group)
  * Not thread-safe against concurrent launches: set it before enqueueing work. */
 #define MHE_OPT_BIG_RIGHT_LOOKING 1
 #define MHE_OPT_DEBUG_SMEM_PAD 2
+#define MHE_OPT_LSM_GROUP 3
 int32_t mhe_set_option(int32_t option, int32_t value);
 
 /* Size in bytes of the device constants buffer for `dims` (0 on bad dims).  The
@@ -692,6 +696,43 @@ int mhe_ls_run(const mhe_ls_dims* dims, int32_t chains, int32_t epochs, const do
                const double* pr, const int32_t* nsat, const double* sat_vel, const double* pr_rate,
                const double* x_init, double* x_out, double* b_out, double* v_out, double* bd_out,
                int32_t* iters_out, double* x_last, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Multi-epoch least squares of a stationary receiver with a linearly drifting
+ * clock (added to ABI v11; no existing struct or function changed).
+ * Replaces utils/leastsquares.py:66-94 (iterativeLeastSquares_multiTimeStep), the
+ * solve behind runBatchLeastSquares (:144-169), for `chains` logs at once: one
+ * position x, a bias b0 at t = 0 and a drift alpha shared by ALL rows of a log,
+ * Gauss-Newton on pr_k - |s_k - x| - b0 - alpha t_k with rows [-los, 1, t_k].
+ * ------------------------------------------------------------------------ */
+typedef struct mhe_lsm_dims {
+  int32_t struct_size; /* = sizeof(mhe_lsm_dims) */
+  int32_t max_iter;    /* maxiter of the reference (default 100); 0: outputs = p_init */
+  double tol;          /* stop after the update when ||dx||_2 < tol, all five components
+                          (reference: 1e-7) */
+} mhe_lsm_dims;
+
+/*
+ * Device pointers; rows are flat, as in the reference function's signature:
+ *   sat_pos (C,row_cap,3) ECEF, pr (C,row_cap), t (C,row_cap): row r of log c holds one
+ *   pseudorange and the time it was taken; nrows (C): rows 0..nrows[c]-1 are valid
+ *   (clamped to row_cap), rows beyond are never read
+ *   p_init (C,5): x (3), b0, alpha to start from
+ * Outputs: p_out (C,5) in the same order; iters_out (C) GN steps taken, or -1 (flagged)
+ * when the log has fewer than 5 rows, all its rows share one value of t (the 1 and t
+ * columns are then parallel), or a Cholesky pivot of the 5x5 normal matrix is not positive.
+ * A flagged log's p_out is its last complete iterate (p_init if the first step fails).
+ * A lane group of 16 or 64 owns one log; which one is a function of row_cap alone
+ * (mhe_ls_multi_group), so a log's result is bitwise the same alone or in any batch.
+ * Stream-ordered: no host synchronisation, no allocation.  Returns MHE_OK or MHE_ERR_*.
+ */
+int mhe_ls_multi_run(const mhe_lsm_dims* dims, int32_t chains, int32_t row_cap, const double* sat_pos,
+                     const double* pr, const double* t, const int32_t* nrows, const double* p_init,
+                     double* p_out, int32_t* iters_out, void* stream);
+
+/* Lanes per log (16 or 64) of the instance mhe_ls_multi_run launches for this row
+ * capacity (MHE_OPT_LSM_GROUP, when set, overrides the rule); MHE_ERR_DIMS if row_cap < 0. */
+int32_t mhe_ls_multi_group(int32_t row_cap);
 
 /* Library version string. */
 const char* mhe_version(void);

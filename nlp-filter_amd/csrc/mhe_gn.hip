@@ -685,8 +685,10 @@ extern "C" {
 int32_t mhe_set_option(int32_t option, int32_t value) {
   int* slot = option == MHE_OPT_BIG_RIGHT_LOOKING ? &g_opt_big_right_looking
               : option == MHE_OPT_DEBUG_SMEM_PAD  ? &g_opt_smem_pad
+              : option == MHE_OPT_LSM_GROUP       ? &g_opt_lsm_group
                                                   : nullptr;
   if (!slot || value < 0 || (option == MHE_OPT_DEBUG_SMEM_PAD && value > 160 * 1024)) return MHE_ERR_DIMS;
+  if (option == MHE_OPT_LSM_GROUP && value != 0 && value != 16 && value != 64) return MHE_ERR_DIMS;
   const int old = *slot;
   *slot = value;
   return old;

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MHE_LIB", os.path.join(HERE, "libmhe.so"))
 MHE_OK = 0
 ERRORS = {-1: "MHE_ERR_DIMS", -2: "MHE_ERR_MODEL", -3: "MHE_ERR_HIP", -4: "MHE_ERR_UNSUPPORTED", -5: "MHE_ERR_NULL"}
 STATUS = {0: "converged", 1: "max_iter", 2: "not_spd", 3: "nonfinite", 4: "bad_constants"}
-OPT_BIG_RIGHT_LOOKING, OPT_DEBUG_SMEM_PAD = 1, 2  # mhe_set_option (A/B runs and tests only)
+OPT_BIG_RIGHT_LOOKING, OPT_DEBUG_SMEM_PAD, OPT_LSM_GROUP = 1, 2, 3  # mhe_set_option (A/B runs and tests only)
 # mhe_dims.force_large (MHE_PATH_*): 2 prefers the fused single-launch kernel for a mixed-row /
 # bordered problem that fits it (k_gn_general); for every other dims it is 0
 PATH_AUTO, PATH_LARGE, PATH_FUSED_GENERAL = 0, 1, 2
@@ -54,6 +54,10 @@ class MheLsDims(_Sized):
     _fields_ = [("struct_size", c_i32), ("slots", c_i32), ("max_iter", c_i32), ("warm", c_i32), ("with_vel", c_i32), ("tol", c_dbl)]
 
 
+class MheLsmDims(_Sized):
+    _fields_ = [("struct_size", c_i32), ("max_iter", c_i32), ("tol", c_dbl)]
+
+
 class MheSolveArgs(_Sized):
     _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("X0", c_vp), ("X_out", c_vp), ("Z0", c_vp), ("Z_out", c_vp),
                 ("U", c_vp), ("u_bstride", c_i64), ("Y", c_vp), ("PAR", c_vp), ("par_bstride", c_i64),
@@ -65,6 +69,7 @@ class MheSolveArgs(_Sized):
 _P = ctypes.POINTER(MheDims)
 _PE = ctypes.POINTER(MheEkfDims)
 _PL = ctypes.POINTER(MheLsDims)
+_PM = ctypes.POINTER(MheLsmDims)
 SIGNATURES = {
     "mhe_version": (ctypes.c_char_p, []),
     "mhe_set_option": (c_i32, [c_i32, c_i32]),
@@ -108,6 +113,8 @@ SIGNATURES = {
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp]),
+    "mhe_ls_multi_run": (ctypes.c_int, [_PM, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mhe_ls_multi_group": (c_i32, [c_i32]),
 }
 
 

@@ -24,7 +24,7 @@
 // large-system path (fg_eligible, mhe_solve).
 
 // ------------------------------------------------------------ layouts
-constexpr int FG_LDS_DOUBLES = 160 * 1024 / 8;  // REG_LDS_LIMIT (mhe_core.h host side asserts it)
+constexpr int FG_LDS_DOUBLES = 160 * 1024 / 8;  // REG_LDS_LIMIT (mhe_launch.h asserts it)
 
 // Constants: the register path's layout for (P, M, n, p = 1, NT) -- k_build_cc fills its Cc
 // (no measurement term: the rows are nonlinear), DA, DB; Phi holds the E <= M epoch rows

@@ -1,6 +1,6 @@
 // libmhe: batched collocation Gauss-Newton for MI355X (gfx950, CDNA4) -- the C-ABI
 // (include/mhe.h), argument checks, constants building and dispatch to the
-// per-pair launch templates (mhe_core.h, pair_*.hip).
+// per-pair launch templates (mhe_launch.h, pair_*.hip).
 //
 // What replaces what (reference kingdwd/nlp-filter):
 //   fixedTimeOptimalEstimationNLP objective   nlp/nlp.py:202-286
@@ -323,6 +323,14 @@ unsigned long long const_tag(const mhe_dims* dm, int NT) {
   return h | 1ull;
 }
 
+// the equality rows of the dims as a kernel argument (NULL eq_rhs = all 0)
+EqPairs eq_pairs(const mhe_dims* dm) {
+  EqPairs e = {};
+  for (int i = 0; i < 2 * dm->n_eq; ++i) e.v[i] = dm->eq_idx[i];
+  for (int i = 0; i < dm->n_eq; ++i) e.r[i] = dm->eq_rhs ? dm->eq_rhs[i] : 0.0;
+  return e;
+}
+
 // Constants of the large-system path: model-independent (D, D^T, D^T C D, weights,
 // the epoch-compressed basis and the equality-constraint pairs).
 int build_big_consts(const mhe_dims* dm, const double* D, const double* cw, const double* Phi, const double* Qw,
@@ -335,34 +343,28 @@ int build_big_consts(const mhe_dims* dm, const double* D, const double* cw, cons
     hipLaunchKernelGGL(k_big_epoch_scan, dim3(1), dim3(1), 0, st, P, dm->M, dm->n, dm->p, cbuf);
     hipLaunchKernelGGL(k_big_epoch_rows, dim3(256), dim3(256), 0, st, P, dm->M, dm->n, dm->p, Phi, cbuf);
   }
-  if (dm->n_eq > 0) {
-    EqPairs e = {};
-    for (int i = 0; i < 2 * dm->n_eq; ++i) e.v[i] = dm->eq_idx[i];
-    for (int i = 0; i < dm->n_eq; ++i) e.r[i] = dm->eq_rhs ? dm->eq_rhs[i] : 0.0;
-    hipLaunchKernelGGL(k_big_eq_consts, dim3(1), dim3(128), 0, st, P, dm->M, dm->n, dm->p, dm->n_eq, e, cbuf);
-  }
+  if (dm->n_eq > 0)
+    hipLaunchKernelGGL(k_big_eq_consts, dim3(1), dim3(128), 0, st, P, dm->M, dm->n, dm->p, dm->n_eq, eq_pairs(dm),
+                       cbuf);
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
-GnArgs make_args(const mhe_dims* dm, const void* cbuf, int NT) {
-  GnArgs a = {};
-#ifdef MHE_DIAG
-  a.dbg = g_dbg;
-#endif
+// The launch arguments both paths derive from the dims and the constants alone (GnArgs and
+// BigArgs name them alike).
+template <class A>
+void set_dims(A& a, const mhe_dims* dm, const void* cbuf, int NT) {
   a.cbuf = (const char*)cbuf;
   a.P = dm->N + 1;
   a.M = dm->M;
-  a.d = a.P * dm->n;
   a.NT = NT;
-  a.ntiles = NT * (NT + 1) / 2;
   a.q = dm->q;
   a.has_prior = dm->has_prior;
-  for (int i = 0; i < 8; ++i) a.idx[i] = dm->meas_idx[i];
   a.alpha = 2.0 / dm->T;
   a.huber_delta = dm->huber_delta;
   a.n_bounds = dm->n_bounds;
   a.tag = const_tag(dm, NT);
   for (int i = 0; i < 8; ++i) {
+    a.idx[i] = dm->meas_idx[i];
     a.bidx[i] = dm->bound_idx[i];
     a.blb[i] = dm->bound_lb[i];
     a.bub[i] = dm->bound_ub[i];
@@ -370,6 +372,25 @@ GnArgs make_args(const mhe_dims* dm, const void* cbuf, int NT) {
   }
   a.nz = dm->n_extra;
   a.nc = dm->n_eq;
+}
+
+// The per-solve inputs of an operating point: the only place a launch struct takes them from
+// mhe_solve_args (the iterate and the outputs are each call's own).
+template <class A>
+void set_point(A& a, const mhe_solve_args* at) {
+  a.U = at->U; a.ustride = at->u_bstride; a.Y = at->Y; a.PAR = at->PAR; a.pstride = at->par_bstride; a.x0 = at->x0;
+  a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.md = at->meas_delta; a.mdstride = at->md_bstride;
+  a.Pw = at->Pw; a.pwstride = at->pw_bstride;
+}
+
+GnArgs make_args(const mhe_dims* dm, const void* cbuf, int NT) {
+  GnArgs a = {};
+#ifdef MHE_DIAG
+  a.dbg = g_dbg;
+#endif
+  set_dims(a, dm, cbuf, NT);
+  a.d = a.P * dm->n;
+  a.ntiles = NT * (NT + 1) / 2;
   return a;
 }
 
@@ -380,11 +401,8 @@ int build_fg_consts(const mhe_dims* dm, int NT, const PairOps* ops, const double
                     const double* Phi, const double* Qw, const double* Rw, const double* Pw, char* cbuf,
                     hipStream_t st) {
   const int P = dm->N + 1;
-  EqPairs e = {};
-  for (int i = 0; i < 2 * dm->n_eq; ++i) e.v[i] = dm->eq_idx[i];
-  for (int i = 0; i < dm->n_eq; ++i) e.r[i] = dm->eq_rhs ? dm->eq_rhs[i] : 0.0;
-  hipLaunchKernelGGL(k_fg_consts, dim3(64), dim3(256), 0, st, P, dm->M, dm->n, NT, dm->n_eq, e, D, cw, Qw, Rw, Pw,
-                     cbuf);
+  hipLaunchKernelGGL(k_fg_consts, dim3(64), dim3(256), 0, st, P, dm->M, dm->n, NT, dm->n_eq, eq_pairs(dm), D, cw, Qw,
+                     Rw, Pw, cbuf);
   int rc = ops->build_cc(dm, NT, D, cw, Phi, Qw, Rw, Pw, cbuf, st);
   if (rc != MHE_OK) return rc;
   if (dm->M > 0) {
@@ -403,24 +421,10 @@ int build_fg_consts(const mhe_dims* dm, int NT, const PairOps* ops, const double
 // constants / workspace alone (the per-solve pointers are set by the caller).
 BigArgs make_big_args(const mhe_dims* dims, const void* cbuf, int NT, void* workspace) {
   BigArgs A = {};
-  A.cbuf = (const char*)cbuf;
-  A.P = dims->N + 1; A.M = dims->M; A.n = dims->n; A.Pp = big_pp(A.P); A.NTc = A.Pp / 16; A.NT = NT;
-  A.q = dims->q; A.has_prior = dims->has_prior;
-  for (int i = 0; i < 8; ++i) A.idx[i] = dims->meas_idx[i];
-  A.alpha = 2.0 / dims->T;
+  set_dims(A, dims, cbuf, NT);
+  A.n = dims->n; A.Pp = big_pp(A.P); A.NTc = A.Pp / 16;
   A.ws = (double*)workspace; A.ws_stride = big_ws_doubles(dims, NT);
-  A.n_bounds = dims->n_bounds;
-  for (int i = 0; i < 8; ++i) {
-    A.bidx[i] = dims->bound_idx[i];
-    A.blb[i] = dims->bound_lb[i];
-    A.bub[i] = dims->bound_ub[i];
-    A.dpar[i] = dims->dyn_par[i];
-  }
-  A.nz = dims->n_extra;
-  A.nc = dims->n_eq;
   A.huber = dims->dyn_cost == MHE_COST_HUBER;
-  A.huber_delta = dims->huber_delta;
-  A.tag = const_tag(dims, NT);
   return A;
 }
 
@@ -442,6 +446,44 @@ int check_pw_arg(const mhe_dims* dims, const double* Pw) {
   if (!Pw) return MHE_OK;
   if (!dims->has_prior || (!is_big(dims) && dims->n > 16)) return MHE_ERR_UNSUPPORTED;
   return MHE_OK;
+}
+
+int check_rows(const mhe_dims* dims, const mhe_solve_args* at) {
+  const int rc = check_row_args(dims, at->Rw, at->meas_delta);
+  return rc != MHE_OK ? rc : check_pw_arg(dims, at->Pw);
+}
+
+// The header of a caller's mhe_solve_args, before any other field is read.  batch = false
+// leaves the batch to check_point (the assemble calls answer for the row inputs first).
+int check_header(const mhe_solve_args* at, bool batch = true) {
+  if (!at) return MHE_ERR_NULL;
+  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  return batch && at->batch < 0 ? MHE_ERR_DIMS : MHE_OK;
+}
+
+// An mhe_solve_args as an operating point of checked dims: the header, the inputs the dims
+// require (Z0 only where the call reads it: need_z), the call's own pointers (outs_ok) and
+// the per-solve row inputs and prior weight.  MHE_OK with at->batch == 0 means "nothing to
+// do": the pointers of an empty batch are not looked at.  A call whose own checks come
+// between the header and the pointers calls check_header first.
+int check_point(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, bool need_z, bool outs_ok) {
+  const int rc = check_header(at);
+  if (rc != MHE_OK || at->batch == 0) return rc;
+  if (!const_buf || !at->X0 || !outs_ok || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) ||
+      (dims->q > 0 && !at->PAR) || (dims->has_prior && !at->x0) || (need_z && !at->Z0))
+    return MHE_ERR_NULL;
+  return check_rows(dims, at);
+}
+
+// The positional entry points' arguments as an operating point (no per-solve row inputs).
+mhe_solve_args pack_point(int32_t batch, const double* X, const double* Z, const double* U, int64_t u_bstride,
+                          const double* Y, const double* PAR, int64_t par_bstride, const double* x0, void* workspace,
+                          size_t workspace_bytes) {
+  mhe_solve_args g = {};
+  g.struct_size = (int32_t)sizeof(mhe_solve_args);
+  g.batch = batch; g.X0 = X; g.Z0 = Z; g.U = U; g.u_bstride = u_bstride; g.Y = Y; g.PAR = PAR;
+  g.par_bstride = par_bstride; g.x0 = x0; g.workspace = workspace; g.workspace_bytes = workspace_bytes;
+  return g;
 }
 
 }  // namespace
@@ -680,6 +722,25 @@ __global__ __launch_bounds__(64) void k_arrival(int n, int P, int batch, const d
 extern "C" void mhe_diag_set_buffer(void* p) { g_dbg = (unsigned long long*)p; }
 #endif
 
+namespace {
+
+// One stage of the large-system path between the state words' init and finish (A.state);
+// pre / post enqueue what a call imports before and exports after the stage.
+template <class Pre, class Post>
+int run_big_stage(const PairOps* ops, const mhe_dims* dims, BigArgs& A, int batch, int stage, hipStream_t st, Pre pre,
+                  Post post) {
+  const int nb = (batch + 255) / 256;
+  hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
+  pre();
+  const int rc = ops->big_stage(dims, A, batch, stage, st);
+  if (rc != MHE_OK) return rc;
+  post();
+  hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, A.state);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t mhe_set_option(int32_t option, int32_t value) {
@@ -761,13 +822,9 @@ int mhe_gn_solve_ext(const mhe_dims* dims, const void* const_buf, int32_t batch,
                      const double* PAR, int64_t par_bstride, const double* x0, double* cost_out, int32_t* iters_out,
                      int32_t* status_out, int32_t max_iter, double tol, void* workspace, size_t workspace_bytes,
                      void* stream) {
-  mhe_solve_args g = {};
-  g.struct_size = (int32_t)sizeof(mhe_solve_args);
-  g.batch = batch; g.X0 = X0; g.X_out = X_out; g.Z0 = Z0; g.Z_out = Z_out; g.U = U; g.u_bstride = u_bstride;
-  g.Y = Y; g.PAR = PAR; g.par_bstride = par_bstride; g.Rw = nullptr; g.rw_bstride = 0; g.x0 = x0;
-  g.cost_out = cost_out; g.iters_out = iters_out; g.status_out = status_out; g.max_iter = max_iter; g.tol = tol;
-  g.workspace = workspace; g.workspace_bytes = workspace_bytes;
-  g.meas_delta = nullptr; g.md_bstride = 0; g.Pw = nullptr; g.pw_bstride = 0;
+  mhe_solve_args g = pack_point(batch, X0, Z0, U, u_bstride, Y, PAR, par_bstride, x0, workspace, workspace_bytes);
+  g.X_out = X_out; g.Z_out = Z_out; g.cost_out = cost_out; g.iters_out = iters_out; g.status_out = status_out;
+  g.max_iter = max_iter; g.tol = tol;
   return mhe_solve(dims, const_buf, &g, stream);
 }
 
@@ -775,18 +832,13 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
-  if (!g) return MHE_ERR_NULL;
-  if (g->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
+  rc = check_header(g);
+  if (rc == MHE_OK && g->max_iter < 0) rc = MHE_ERR_DIMS;
+  if (rc == MHE_OK)
+    rc = check_point(dims, const_buf, g, dims->n_extra > 0,
+                     g->X_out && g->cost_out && g->iters_out && g->status_out && (dims->n_extra == 0 || g->Z_out));
+  if (rc != MHE_OK || g->batch == 0) return rc;
   const int batch = g->batch;
-  if (batch < 0 || g->max_iter < 0) return MHE_ERR_DIMS;
-  if (batch == 0) return MHE_OK;
-  if (!const_buf || !g->X0 || !g->X_out || !g->cost_out || !g->iters_out || !g->status_out ||
-      (dims->M > 0 && !g->Y) || (dims->m > 0 && !g->U) || (dims->q > 0 && !g->PAR) || (dims->has_prior && !g->x0) ||
-      (dims->n_extra > 0 && (!g->Z0 || !g->Z_out)))
-    return MHE_ERR_NULL;
-  rc = check_row_args(dims, g->Rw, g->meas_delta);  // per-solve weights / robust rows
-  if (rc == MHE_OK) rc = check_pw_arg(dims, g->Pw);
-  if (rc != MHE_OK) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -795,9 +847,7 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
   if (is_big(dims)) {
     if (!g->workspace || g->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
     BigArgs A = make_big_args(dims, const_buf, NT, g->workspace);
-    A.U = g->U; A.ustride = g->u_bstride; A.Y = g->Y; A.PAR = g->PAR; A.pstride = g->par_bstride; A.x0 = g->x0;
-    A.Rw = g->Rw; A.rwstride = g->rw_bstride; A.md = g->meas_delta; A.mdstride = g->md_bstride;
-    A.Pw = g->Pw; A.pwstride = g->pw_bstride;
+    set_point(A, g);
     A.X = g->X_out; A.cost = g->cost_out; A.iters = g->iters_out; A.state = g->status_out; A.tol = g->tol;
     A.Z = g->Z_out;
     A.lam = dims->n_eq > 0 ? g->lambda_out : nullptr;
@@ -814,10 +864,9 @@ int mhe_solve(const mhe_dims* dims, const void* const_buf, const mhe_solve_args*
     return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
   }
   GnArgs a = make_args(dims, const_buf, NT);
-  a.X0 = g->X0; a.Xout = g->X_out; a.U = g->U; a.ustride = g->u_bstride; a.Y = g->Y; a.PAR = g->PAR;
-  a.pstride = g->par_bstride; a.x0 = g->x0; a.cost = g->cost_out; a.iters = g->iters_out; a.status = g->status_out;
-  a.max_iter = g->max_iter; a.tol = g->tol; a.Rw = g->Rw; a.rwstride = g->rw_bstride;
-  a.md = g->meas_delta; a.mdstride = g->md_bstride; a.Pw = g->Pw; a.pwstride = g->pw_bstride;
+  set_point(a, g);
+  a.X0 = g->X0; a.Xout = g->X_out; a.cost = g->cost_out; a.iters = g->iters_out; a.status = g->status_out;
+  a.max_iter = g->max_iter; a.tol = g->tol;
   if (fused) {
     a.Z0 = g->Z0; a.Zout = g->Z_out;
     a.lam = dims->n_eq > 0 ? g->lambda_out : nullptr;
@@ -838,6 +887,39 @@ size_t mhe_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_quer
   return sizeof(double) * (cov_cost_doubles(batch) + (size_t)batch * KP * 16 * NT);
 }
 
+// mixed rows, extra variables or equality rows: the problems mhe_state_cov / mhe_arrival refuse
+static bool is_general(const mhe_dims* dims) {
+  return dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED;
+}
+
+// mhe_state_cov's and mhe_kkt_cov's checks of the operating point and the query
+static int check_cov_args(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* PhiQ,
+                          int32_t n_query, const double* cov_out, const int32_t* status_out) {
+  int rc = check_header(at);
+  if (rc == MHE_OK && n_query <= 0) rc = MHE_ERR_DIMS;
+  if (rc == MHE_OK && (!PhiQ || !cov_out || !status_out)) rc = MHE_ERR_NULL;
+  return rc != MHE_OK ? rc : check_point(dims, const_buf, at, dims->n_extra > 0, true);  // rows as mhe_solve
+}
+
+// The covariance stage on the large-system path (BIG_STAGE_COV, or BIG_STAGE_KKT_COV at
+// (X, Z) with the extra variables' block in covz_out).
+static int big_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, int NT, const PairOps* ops,
+                   int stage, const double* PhiQ, int32_t n_query, double* cov_out, double* covz_out,
+                   int32_t* status_out, void* scratch, size_t scratch_bytes, hipStream_t st) {
+  const int batch = at->batch;
+  if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
+  if (!scratch || scratch_bytes < mhe_cov_scratch_bytes(dims, batch, n_query)) return MHE_ERR_NULL;
+  BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
+  A.n_bounds = 0;  // the unconstrained GN model at X, under its equality rows (bounds are not reflected)
+  set_point(A, at);
+  A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
+  if (stage == BIG_STAGE_KKT_COV) A.Z = const_cast<double*>(at->Z0);  // read only by k_big_resid
+  A.cost = (double*)scratch; A.state = status_out;
+  A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
+  A.covz = dims->n_extra > 0 ? covz_out : nullptr;
+  return run_big_stage(ops, dims, A, batch, stage, st, [] {}, [] {});
+}
+
 int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* PhiQ,
                   int32_t n_query, double* cov_out, int32_t* status_out, void* scratch, size_t scratch_bytes,
                   void* stream) {
@@ -845,79 +927,24 @@ int mhe_state_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_a
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
   // a covariance under constraints is a projected quantity: not this call's
-  if (dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED) return MHE_ERR_UNSUPPORTED;
-  if (!at) return MHE_ERR_NULL;
-  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
-  const int batch = at->batch;
-  if (batch < 0 || n_query <= 0) return MHE_ERR_DIMS;
-  if (!PhiQ || !cov_out || !status_out) return MHE_ERR_NULL;
-  if (batch == 0) return MHE_OK;
-  if (!const_buf || !at->X0 || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) || (dims->q > 0 && !at->PAR) ||
-      (dims->has_prior && !at->x0))
-    return MHE_ERR_NULL;
-  rc = check_row_args(dims, at->Rw, at->meas_delta);  // as mhe_solve
-  if (rc == MHE_OK) rc = check_pw_arg(dims, at->Pw);
-  if (rc != MHE_OK) return rc;
+  if (is_general(dims)) return MHE_ERR_UNSUPPORTED;
+  rc = check_cov_args(dims, const_buf, at, PhiQ, n_query, cov_out, status_out);
+  if (rc != MHE_OK || at->batch == 0) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (is_big(dims)) {
-    if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
-    if (!scratch || scratch_bytes < mhe_cov_scratch_bytes(dims, batch, n_query)) return MHE_ERR_NULL;
-    BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
-    A.n_bounds = 0;  // the unconstrained GN model at X (bounds are not reflected)
-    A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
-    A.Rw = at->Rw; A.rwstride = at->rw_bstride; A.md = at->meas_delta; A.mdstride = at->md_bstride;
-    A.Pw = at->Pw; A.pwstride = at->pw_bstride;
-    A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
-    A.cost = (double*)scratch; A.state = status_out;
-    A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
-    const int nb = (batch + 255) / 256;
-    hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
-    rc = ops->big_stage(dims, A, batch, BIG_STAGE_COV, st);
-    if (rc != MHE_OK) return rc;
-    hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status_out);
-    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
-  }
+  if (is_big(dims))
+    return big_cov(dims, const_buf, at, NT, ops, BIG_STAGE_COV, PhiQ, n_query, cov_out, nullptr, status_out, scratch,
+                   scratch_bytes, st);
   GnArgs a = make_args(dims, const_buf, NT);
-  a.X0 = at->X0; a.U = at->U; a.ustride = at->u_bstride; a.Y = at->Y; a.PAR = at->PAR; a.pstride = at->par_bstride;
-  a.x0 = at->x0; a.Rw = at->Rw; a.rwstride = at->rw_bstride; a.md = at->meas_delta; a.mdstride = at->md_bstride;
-  a.Pw = at->Pw; a.pwstride = at->pw_bstride;
+  set_point(a, at);
+  a.X0 = at->X0;
   a.status = status_out;
   a.PhiQ = PhiQ; a.nq = n_query; a.cov = cov_out;
-  return ops->gn(dims, a, batch, MODE_COV, st);
+  return ops->gn(dims, a, at->batch, MODE_COV, st);
 }
 
 size_t mhe_arrival_scratch_bytes(const mhe_dims* dims, int32_t batch) { return mhe_cov_scratch_bytes(dims, batch, 1); }
-
-int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
-                double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
-                size_t scratch_bytes, void* stream) {
-  int NT = 0;
-  int rc = check_dims(dims, &NT);
-  if (rc != MHE_OK) return rc;
-  if (dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED || dims->n > ARR_NMAX)
-    return MHE_ERR_UNSUPPORTED;
-  if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_state_cov: one 16-column panel
-  if (!at) return MHE_ERR_NULL;
-  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
-  if (at->batch < 0) return MHE_ERR_DIMS;
-  if (!phi || !x_arr || !Pw_arr || !status_out) return MHE_ERR_NULL;
-  if (at->batch == 0) return MHE_OK;
-  // the covariance stage of mhe_state_cov, one query: the block into cov_out when the caller
-  // wants it, else into Pw_arr, which k_arrival then inverts in place
-  double* cov = cov_out ? cov_out : Pw_arr;
-  rc = mhe_state_cov(dims, const_buf, at, phi, 1, cov, status_out, scratch, scratch_bytes, stream);
-  if (rc != MHE_OK) return rc;
-  hipLaunchKernelGGL(k_arrival, dim3(at->batch), dim3(64), 0, (hipStream_t)stream, dims->n, dims->N + 1, at->batch,
-                     at->X0, phi, cov, Pw_arr, x_arr, status_out);
-  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
-}
-
-// mixed rows, extra variables or equality rows: the problems mhe_state_cov / mhe_arrival refuse
-static bool is_general(const mhe_dims* dims) {
-  return dims->n_extra > 0 || dims->n_eq > 0 || dims->meas_model == MHE_MEAS_MIXED;
-}
 
 size_t mhe_kkt_cov_scratch_bytes(const mhe_dims* dims, int32_t batch, int32_t n_query) {
   // the query columns, as mhe_state_cov's; the border columns live in the workspace (ZM)
@@ -934,62 +961,53 @@ int mhe_kkt_cov(const mhe_dims* dims, const void* const_buf, const mhe_solve_arg
   if (!is_general(dims))  // no border, typed rows: mhe_state_cov itself (both paths)
     return mhe_state_cov(dims, const_buf, at, PhiQ, n_query, cov_out, status_out, scratch, scratch_bytes, stream);
   if (!is_big(dims)) return MHE_ERR_UNSUPPORTED;  // every general problem takes the large-system path
-  if (!at) return MHE_ERR_NULL;
-  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
-  const int batch = at->batch;
-  if (batch < 0 || n_query <= 0) return MHE_ERR_DIMS;
-  if (!PhiQ || !cov_out || !status_out) return MHE_ERR_NULL;
-  if (batch == 0) return MHE_OK;
-  if (!const_buf || !at->X0 || (dims->M > 0 && !at->Y) || (dims->m > 0 && !at->U) || (dims->q > 0 && !at->PAR) ||
-      (dims->has_prior && !at->x0) || (dims->n_extra > 0 && !at->Z0))
-    return MHE_ERR_NULL;
-  rc = check_row_args(dims, at->Rw, at->meas_delta);  // as mhe_solve
-  if (rc == MHE_OK) rc = check_pw_arg(dims, at->Pw);
-  if (rc != MHE_OK) return rc;
+  rc = check_cov_args(dims, const_buf, at, PhiQ, n_query, cov_out, status_out);
+  if (rc != MHE_OK || at->batch == 0) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
-  if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
-  if (!scratch || scratch_bytes < mhe_kkt_cov_scratch_bytes(dims, batch, n_query)) return MHE_ERR_NULL;
-  hipStream_t st = (hipStream_t)stream;
-  BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
-  A.n_bounds = 0;  // the GN model at X under its equality rows (bounds are not reflected)
-  A.U = at->U; A.ustride = at->u_bstride; A.Y = at->Y; A.PAR = at->PAR; A.pstride = at->par_bstride; A.x0 = at->x0;
-  A.Rw = at->Rw; A.rwstride = at->rw_bstride; A.md = at->meas_delta; A.mdstride = at->md_bstride;
-  A.Pw = at->Pw; A.pwstride = at->pw_bstride;
-  A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
-  A.Z =const_cast<double*>(at->Z0);  // read only by k_big_resid
-  A.cost = (double*)scratch; A.state = status_out;
-  A.PhiQ = PhiQ; A.nq = n_query; A.cov = cov_out; A.cov_scratch = (double*)scratch + cov_cost_doubles(batch);
-  A.covz = dims->n_extra > 0 ? covz_out : nullptr;
-  const int nb = (batch + 255) / 256;
-  hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
-  rc = ops->big_stage(dims, A, batch, BIG_STAGE_KKT_COV, st);
+  return big_cov(dims, const_buf, at, NT, ops, BIG_STAGE_KKT_COV, PhiQ, n_query, cov_out, covz_out, status_out,
+                 scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+// mhe_arrival / mhe_kkt_arrival after their dims checks: the covariance stage of mhe_state_cov
+// (kkt: mhe_kkt_cov), one query -- the block into cov_out when the caller wants it, else into
+// Pw_arr -- and k_arrival, which inverts it in place.
+static int arrival(bool kkt, const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at,
+                   const double* phi, double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out,
+                   void* scratch, size_t scratch_bytes, void* stream) {
+  int rc = check_header(at);
   if (rc != MHE_OK) return rc;
-  hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status_out);
+  if (!phi || !x_arr || !Pw_arr || !status_out) return MHE_ERR_NULL;
+  if (at->batch == 0) return MHE_OK;
+  double* cov = cov_out ? cov_out : Pw_arr;
+  rc = kkt ? mhe_kkt_cov(dims, const_buf, at, phi, 1, cov, nullptr, status_out, scratch, scratch_bytes, stream)
+           : mhe_state_cov(dims, const_buf, at, phi, 1, cov, status_out, scratch, scratch_bytes, stream);
+  if (rc != MHE_OK) return rc;
+  hipLaunchKernelGGL(k_arrival, dim3(at->batch), dim3(64), 0, (hipStream_t)stream, dims->n, dims->N + 1, at->batch,
+                     at->X0, phi, cov, Pw_arr, x_arr, status_out);
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
+int mhe_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
+                double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
+                size_t scratch_bytes, void* stream) {
+  const int rc = check_dims(dims, nullptr);
+  if (rc != MHE_OK) return rc;
+  if (is_general(dims) || dims->n > ARR_NMAX) return MHE_ERR_UNSUPPORTED;
+  if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_state_cov: one 16-column panel
+  return arrival(false, dims, const_buf, at, phi, x_arr, Pw_arr, cov_out, status_out, scratch, scratch_bytes, stream);
 }
 
 int mhe_kkt_arrival(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, const double* phi,
                     double* x_arr, double* Pw_arr, double* cov_out, int32_t* status_out, void* scratch,
                     size_t scratch_bytes, void* stream) {
-  int NT = 0;
-  int rc = check_dims(dims, &NT);
+  const int rc = check_dims(dims, nullptr);
   if (rc != MHE_OK) return rc;
   if (fg_eligible(dims)) return MHE_ERR_UNSUPPORTED;  // k_gn_general solves only
   // an equality row between state components makes the block rank-deficient: no inverse
   if (dims->n_eq > 0 || dims->n > ARR_NMAX) return MHE_ERR_UNSUPPORTED;
   if (!is_big(dims) && dims->n > 16) return MHE_ERR_UNSUPPORTED;  // as mhe_arrival
-  if (!at) return MHE_ERR_NULL;
-  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
-  if (at->batch < 0) return MHE_ERR_DIMS;
-  if (!phi || !x_arr || !Pw_arr || !status_out) return MHE_ERR_NULL;
-  if (at->batch == 0) return MHE_OK;
-  double* cov = cov_out ? cov_out : Pw_arr;  // as mhe_arrival: k_arrival inverts in place
-  rc = mhe_kkt_cov(dims, const_buf, at, phi, 1, cov, nullptr, status_out, scratch, scratch_bytes, stream);
-  if (rc != MHE_OK) return rc;
-  hipLaunchKernelGGL(k_arrival, dim3(at->batch), dim3(64), 0, (hipStream_t)stream, dims->n, dims->N + 1, at->batch,
-                     at->X0, phi, cov, Pw_arr, x_arr, status_out);
-  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  return arrival(true, dims, const_buf, at, phi, x_arr, Pw_arr, cov_out, status_out, scratch, scratch_bytes, stream);
 }
 
 int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
@@ -1017,33 +1035,30 @@ int mhe_resjac(const mhe_dims* dims, const void* const_buf, int32_t batch, const
   return ops->resjac(a, batch, (hipStream_t)stream);
 }
 
-// mhe_assemble with the per-solve row inputs (mhe_assemble_at); the positional call passes none
-static int assemble_reg(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
-                        int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
-                        const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride,
-                        const double* Pw, int64_t pw_bstride, double* H, double* g, double* cost, void* stream) {
+// mhe_assemble at an operating point (mhe_assemble_at's register path; the positional call
+// passes no per-solve row inputs)
+static int assemble_reg(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, double* H, double* g,
+                        double* cost, void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
   if (is_big(dims)) return MHE_ERR_UNSUPPORTED;  // kernel-level parity APIs: register path only
-  if (batch <= 0) return batch == 0 ? MHE_OK : MHE_ERR_DIMS;
-  if (!const_buf || !X || !H || !g || !cost || (dims->M > 0 && !Y) || (dims->m > 0 && !U) ||
-      (dims->q > 0 && !PAR) || (dims->has_prior && !x0))
-    return MHE_ERR_NULL;
+  rc = check_point(dims, const_buf, at, false, H && g && cost);
+  if (rc != MHE_OK || at->batch == 0) return rc;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
   GnArgs a = make_args(dims, const_buf, NT);
-  a.X0 = X; a.U = U; a.ustride = u_bstride; a.Y = Y; a.PAR = PAR; a.pstride = par_bstride; a.x0 = x0;
+  set_point(a, at);
+  a.X0 = at->X0;
   a.Hout = H; a.gout = g; a.cost = cost;
-  a.Rw = Rw; a.rwstride = rw_bstride; a.md = md; a.mdstride = md_bstride; a.Pw = Pw; a.pwstride = pw_bstride;
-  return ops->gn(dims, a, batch, MODE_ASSEMBLE, (hipStream_t)stream);
+  return ops->gn(dims, a, at->batch, MODE_ASSEMBLE, (hipStream_t)stream);
 }
 
 int mhe_assemble(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* U,
                  int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride, const double* x0,
                  double* H, double* g, double* cost, void* stream) {
-  return assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0,
-                      nullptr, 0, H, g, cost, stream);
+  const mhe_solve_args at = pack_point(batch, X, nullptr, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0);
+  return assemble_reg(dims, const_buf, &at, H, g, cost, stream);
 }
 
 int mhe_chol_solve(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,
@@ -1120,72 +1135,56 @@ int32_t mhe_kkt_dim(const mhe_dims* dims) {
   return dp < 0 ? dp : dp + dims->n_extra + dims->n_eq;
 }
 
-// mhe_assemble_kkt_ws with the per-solve row inputs (mhe_assemble_at); the positional call passes none
-static int assemble_kkt(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
-                        const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
-                        const double* x0, const double* Rw, int64_t rw_bstride, const double* md, int64_t md_bstride,
-                        const double* Pw, int64_t pw_bstride, double* H, double* g, double* cost, int32_t* status,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+// mhe_assemble_kkt_ws at an operating point (mhe_assemble_at; the positional call passes no
+// per-solve row inputs).  The row inputs are answered for before the batch and the pointers.
+static int assemble_kkt(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, double* H, double* g,
+                        double* cost, int32_t* status, void* stream) {
   int NT = 0;
   int rc = check_dims(dims, &NT);
   if (rc != MHE_OK) return rc;
-  rc = check_row_args(dims, Rw, md);
-  if (rc == MHE_OK) rc = check_pw_arg(dims, Pw);
+  rc = check_header(at, false);
+  if (rc == MHE_OK) rc = check_rows(dims, at);
   if (rc != MHE_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
+  const int batch = at->batch;
   if (!is_big(dims)) {
-    rc = assemble_reg(dims, const_buf, batch, X, U, u_bstride, Y, PAR, par_bstride, x0, Rw, rw_bstride, md, md_bstride,
-                      Pw, pw_bstride, H, g, cost, stream);
+    rc = assemble_reg(dims, const_buf, at, H, g, cost, stream);
     if (rc == MHE_OK && status && batch > 0 && hipMemsetAsync(status, 0, sizeof(int32_t) * batch, st) != hipSuccess)
       return MHE_ERR_HIP;
     return rc;
   }
-  if (batch <= 0) return batch == 0 ? MHE_OK : MHE_ERR_DIMS;
-  if (!const_buf || !X || !H || !g || !cost || !status || (dims->M > 0 && !Y) || (dims->m > 0 && !U) ||
-      (dims->q > 0 && !PAR) || (dims->has_prior && !x0) || (dims->n_extra > 0 && !Z))
-    return MHE_ERR_NULL;
-  if (!workspace || workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
+  rc = check_point(dims, const_buf, at, dims->n_extra > 0, H && g && cost && status);
+  if (rc != MHE_OK || batch == 0) return rc;
+  if (!at->workspace || at->workspace_bytes < mhe_workspace_bytes(dims, batch)) return MHE_ERR_NULL;
   const PairOps* ops = find_pair(dims);
   if (!ops) return MHE_ERR_UNSUPPORTED;
-  BigArgs A = make_big_args(dims, const_buf, NT, workspace);
+  BigArgs A = make_big_args(dims, const_buf, NT, at->workspace);
   A.n_bounds = 0;  // the plain GN system: the projected method's reduction belongs to the solve
-  A.U = U; A.ustride = u_bstride; A.Y = Y; A.PAR = PAR; A.pstride = par_bstride; A.x0 = x0;
-  A.Rw = Rw; A.rwstride = rw_bstride; A.md = md; A.mdstride = md_bstride; A.Pw = Pw; A.pwstride = pw_bstride;
-  A.X = const_cast<double*>(X);  // read only by k_big_resid / k_big_assemble
-  A.Z = const_cast<double*>(Z);  // read only by k_big_resid
+  set_point(A, at);
+  A.X = const_cast<double*>(at->X0);  // read only by k_big_resid / k_big_assemble
+  A.Z = const_cast<double*>(at->Z0);  // read only by k_big_resid
   A.cost = cost; A.state = status;
-  const int nb = (batch + 255) / 256;
-  hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
-  rc = ops->big_stage(dims, A, batch, BIG_STAGE_ASSEMBLE, st);
-  if (rc != MHE_OK) return rc;
-  const size_t dp = (size_t)A.n * A.Pp;
-  const int K = A.nz + A.nc;
-  const size_t gx0 = (dp * dp + 255) / 256;
-  const unsigned gx = (unsigned)(gx0 < 8192 ? gx0 : 8192);
-  hipLaunchKernelGGL(k_big_export_hg, dim3(gx, batch), dim3(256), 0, st, A, batch, (int)dp + K, H, g);
-  if (K > 0) hipLaunchKernelGGL(k_big_export_border, dim3(K, batch), dim3(256), 0, st, A, batch, dims->p, H, g);
-  hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status);
-  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  return run_big_stage(ops, dims, A, batch, BIG_STAGE_ASSEMBLE, st, [] {}, [&] {
+    const size_t dp = (size_t)A.n * A.Pp;
+    const int K = A.nz + A.nc;
+    const size_t gx0 = (dp * dp + 255) / 256;
+    const unsigned gx = (unsigned)(gx0 < 8192 ? gx0 : 8192);
+    hipLaunchKernelGGL(k_big_export_hg, dim3(gx, batch), dim3(256), 0, st, A, batch, (int)dp + K, H, g);
+    if (K > 0) hipLaunchKernelGGL(k_big_export_border, dim3(K, batch), dim3(256), 0, st, A, batch, dims->p, H, g);
+  });
 }
 
 int mhe_assemble_kkt_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* X, const double* Z,
                         const double* U, int64_t u_bstride, const double* Y, const double* PAR, int64_t par_bstride,
                         const double* x0, double* H, double* g, double* cost, int32_t* status, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  return assemble_kkt(dims, const_buf, batch, X, Z, U, u_bstride, Y, PAR, par_bstride, x0, nullptr, 0, nullptr, 0,
-                      nullptr, 0, H, g, cost, status, workspace, workspace_bytes, stream);
+  const mhe_solve_args at = pack_point(batch, X, Z, U, u_bstride, Y, PAR, par_bstride, x0, workspace, workspace_bytes);
+  return assemble_kkt(dims, const_buf, &at, H, g, cost, status, stream);
 }
 
 int mhe_assemble_at(const mhe_dims* dims, const void* const_buf, const mhe_solve_args* at, double* H, double* g,
                     double* cost, int32_t* status, void* stream) {
-  int NT = 0;
-  const int rc = check_dims(dims, &NT);
-  if (rc != MHE_OK) return rc;
-  if (!at) return MHE_ERR_NULL;
-  if (at->struct_size != (int32_t)sizeof(mhe_solve_args)) return MHE_ERR_DIMS;
-  return assemble_kkt(dims, const_buf, at->batch, at->X0, at->Z0, at->U, at->u_bstride, at->Y, at->PAR,
-                      at->par_bstride, at->x0, at->Rw, at->rw_bstride, at->meas_delta, at->md_bstride, at->Pw,
-                      at->pw_bstride, H, g, cost, status, at->workspace, at->workspace_bytes, stream);
+  return assemble_kkt(dims, const_buf, at, H, g, cost, status, stream);
 }
 
 int mhe_chol_solve_ws(const mhe_dims* dims, const void* const_buf, int32_t batch, const double* H, const double* g,
@@ -1207,16 +1206,18 @@ int mhe_chol_solve_ws(const mhe_dims* dims, const void* const_buf, int32_t batch
   A.border_import = 1;  // K > 0: the caller's border, not one formed at an iterate
   A.lam = nullptr;
   const int K = A.nz + A.nc, ld = A.n * A.Pp + K;
-  const int nb = (batch + 255) / 256;
-  hipLaunchKernelGGL(k_big_parity_init, dim3(nb), dim3(256), 0, st, A, batch);
-  hipLaunchKernelGGL(k_big_import_hg, dim3(NT * (NT + 1) / 2, batch), dim3(256), 0, st, A, batch, ld, H, g);
-  if (K > 0) hipLaunchKernelGGL(k_big_import_border, dim3((K + 15) / 16 * 16, batch), dim3(256), 0, st, A, batch, H, g);
-  rc = ops->big_stage(dims, A, batch, BIG_STAGE_FACTOR, st);
-  if (rc != MHE_OK) return rc;
-  const long long ne = (long long)batch * ld;
-  hipLaunchKernelGGL(k_big_export_delta, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, A, batch, ld, delta);
-  hipLaunchKernelGGL(k_big_parity_finish, dim3(nb), dim3(256), 0, st, batch, status);
-  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  return run_big_stage(
+      ops, dims, A, batch, BIG_STAGE_FACTOR, st,
+      [&] {
+        hipLaunchKernelGGL(k_big_import_hg, dim3(NT * (NT + 1) / 2, batch), dim3(256), 0, st, A, batch, ld, H, g);
+        if (K > 0)
+          hipLaunchKernelGGL(k_big_import_border, dim3((K + 15) / 16 * 16, batch), dim3(256), 0, st, A, batch, H, g);
+      },
+      [&] {
+        const long long ne = (long long)batch * ld;
+        hipLaunchKernelGGL(k_big_export_delta, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, A, batch, ld,
+                           delta);
+      });
 }
 
 }  // extern "C"

@@ -57,6 +57,47 @@ def _handle(s):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+# the device inputs BatchSolver.prepare stages (U and PAR with their batch strides, 0 = shared)
+Staged = collections.namedtuple("Staged", "X B U ustr Y PAR pstr x0")
+
+
+class _Point:
+    """Everything one operating point stages on the device: the ``Staged`` inputs, the extra
+    variables ``Z`` (and where a solve writes them, ``Z_out``) and the per-solve ``Rw``,
+    ``meas_delta`` and ``Pw`` with their batch strides.  ``args`` is the one place an
+    ``MheSolveArgs`` is filled from them; ``tensors`` is what a launch must keep alive."""
+
+    def __init__(self, solver, staged, Z=None, Z_out=None, Rw=None, meas_delta=None, Pw=None):
+        self.solver, self.staged, self.B = solver, staged, staged.B
+        self.Z, self.Z_out = Z, Z_out
+        self.Rw, self.rstr = solver._rw(Rw, self.B)
+        self.md, self.mstr = solver._md(meas_delta, self.B)
+        self.Pw, self.wstr = solver._pw(Pw, self.B)
+
+    @property
+    def tensors(self):
+        g = self.staged
+        return g.X, self.Z, self.Z_out, g.U, g.Y, g.PAR, self.Rw, self.md, self.Pw, g.x0
+
+    def args(self, lo, c, ws, nb):
+        """``MheSolveArgs`` of the trajectories [lo, lo + c) over the workspace (ws, nb); the
+        outputs and iteration limits of a solve are the caller's to add."""
+        s, g = self.solver, self.staged
+        a = _lib.MheSolveArgs()
+        a.batch = c
+        a.X0 = _at(g.X, lo, s.P * s.n)
+        a.Z0, a.Z_out = _at(self.Z, lo, s.n_extra), _at(self.Z_out, lo, s.n_extra)
+        a.U, a.u_bstride = _at(g.U, lo, g.ustr), g.ustr
+        a.Y = _at(g.Y, lo, s.M * s.p)
+        a.PAR, a.par_bstride = _at(g.PAR, lo, g.pstr), g.pstr
+        a.x0 = _at(g.x0, lo, s.n)
+        a.Rw, a.rw_bstride = _at(self.Rw, lo, self.rstr), self.rstr
+        a.meas_delta, a.md_bstride = _at(self.md, lo, self.mstr), self.mstr
+        a.Pw, a.pw_bstride = _at(self.Pw, lo, self.wstr), self.wstr
+        a.workspace, a.workspace_bytes = _ptr(ws), nb
+        return a
+
+
 class BatchSolver:
     """Device constants + launch wrappers for one problem structure.
 
@@ -273,7 +314,7 @@ class BatchSolver:
         x0_t = None
         if self.dims.has_prior:
             x0_t = _dev(x0, dev, (B, self.n))
-        return X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t
+        return Staged(X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t)
 
     @property
     def large_system(self):
@@ -326,6 +367,13 @@ class BatchSolver:
             # after that stream's work is done
             self._ws.popitem(last=False)
         return ws, nb
+
+    def _chunks(self, B, s):
+        """(chunk, ws, nb, [(lo, c), ...]): the launches that stream B trajectories through one
+        workspace on stream s -- the outputs are written in place at each chunk's offset."""
+        chunk = max(1, self._chunk(B, s))
+        ws, nb = self._workspace(chunk, s)
+        return chunk, ws, nb, [(lo, min(chunk, B - lo)) for lo in range(0, B, chunk)]
 
     def _rw(self, Rw, B):
         """Per-solve measurement weights (mhe_solve_args.Rw): (B|1, M, p, p), or (B|1, M)
@@ -394,45 +442,20 @@ class BatchSolver:
             raise ValueError("Pw must be symmetric (every (n, n) block equal to its transpose)")
         return t, (0 if t.shape[0] == 1 else n * n)
 
-    def _gn(self, s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
-            Z=None, Zo=None, Rw=None, lam=None, meas_delta=None, Pw=None):
-        Rw_t, rstr = self._rw(Rw, B)
-        md_t, mstr = self._md(meas_delta, B)
-        Pw_t, wstr = self._pw(Pw, B)
-        if B == 0:
+    def _gn(self, s, cur, pt, outs, max_iter, tol, lam=None):
+        if pt.B == 0:
             return
-        chunk = self._chunk(B, s)
-        ws, nb = self._workspace(chunk, s)
-        P, n, M = self.P, self.n, self.M
-        for lo in range(0, B, chunk):
-            c = min(chunk, B - lo)
-            a = _lib.MheSolveArgs()
-
-            def at(t, per, stride=None):
-                if t is None:
-                    return None
-                st = per if stride is None else stride
-                return ctypes.c_void_p(t.data_ptr() + 8 * lo * st) if st else ctypes.c_void_p(t.data_ptr())
-
-            a.batch = c
-            a.X0, a.X_out = at(X, P * n), at(Xo, P * n)
-            a.Z0, a.Z_out = at(Z, self.n_extra), at(Zo, self.n_extra)
-            a.U, a.u_bstride = at(U_t, 0, ustr), ustr
-            a.Y = at(Y_t, M * self.p)
-            a.PAR, a.par_bstride = at(PAR_t, 0, pstr), pstr
-            a.Rw, a.rw_bstride = at(Rw_t, 0, rstr), rstr
-            a.x0 = at(x0_t, n)
-            a.cost_out = at(cost, 1)
-            a.iters_out = ctypes.c_void_p(iters.data_ptr() + 4 * lo)
-            a.status_out = ctypes.c_void_p(status.data_ptr() + 4 * lo)
+        Xo, cost, iters, status = outs
+        _, ws, nb, spans = self._chunks(pt.B, s)
+        for lo, c in spans:
+            a = pt.args(lo, c, ws, nb)
+            a.X_out = _at(Xo, lo, self.P * self.n)
+            a.cost_out, a.iters_out, a.status_out = _at(cost, lo, 1), _at(iters, lo, 1, 4), _at(status, lo, 1, 4)
             a.max_iter, a.tol = int(max_iter), float(tol)
-            a.workspace, a.workspace_bytes = (None if ws is None else ctypes.c_void_p(ws.data_ptr())), nb
-            a.lambda_out = at(lam, self.n_eq)
-            a.meas_delta, a.md_bstride = at(md_t, 0, mstr), mstr
-            a.Pw, a.pw_bstride = at(Pw_t, 0, wstr), wstr
+            a.lambda_out = _at(lam, lo, self.n_eq)
             rc = self.lib.mhe_solve(self.dims, _ptr(self.cbuf), ctypes.byref(a), _handle(s))
             _lib.check(rc, "mhe_solve")
-        keep_alive(s, cur, X, Xo, Z, Zo, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, cost, iters, status, ws, lam)
+        keep_alive(s, cur, *pt.tensors, Xo, cost, iters, status, ws, lam)
 
     # ------------------------------------------------------------------ calls
     def solve(self, X0, U, Y, PAR=None, x0=None, max_iter=20, tol=1e-10, stream=None, out=None, Z0=None, Rw=None,
@@ -460,7 +483,8 @@ class BatchSolver:
             self.lam = sib.lam
             return r
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X0, U, Y, PAR, x0)
+            staged = self._inputs(X0, U, Y, PAR, x0)
+            X, B = staged.X, staged.B
             if out is None:
                 Xo = torch.empty_like(X)
                 cost = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -481,8 +505,8 @@ class BatchSolver:
                     lam.zero_()
                 else:
                     lam = torch.zeros((B, self.n_eq), dtype=torch.float64, device=self.device)
-            self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol, Z, Zo,
-                     Rw, lam, meas_delta, Pw)
+            self._gn(s, cur, _Point(self, staged, Z, Zo, Rw, meas_delta, Pw), (Xo, cost, iters, status), max_iter,
+                     tol, lam)
             self.lam = lam
         if self.n_extra:
             return Xo, cost, iters, status, Zo
@@ -493,12 +517,10 @@ class BatchSolver:
         return self._inputs(X0, U, Y, PAR, x0)
 
     def solve_staged(self, staged, outs, max_iter, tol, stream=None, meas_delta=None, Pw=None):
-        X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = staged
-        Xo, cost, iters, status = outs
         self._check_ready()
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            self._gn(s, cur, B, X, Xo, U_t, ustr, Y_t, PAR_t, pstr, x0_t, cost, iters, status, max_iter, tol,
-                     meas_delta=meas_delta, Pw=Pw)
+            staged = staged if isinstance(staged, Staged) else Staged(*staged)
+            self._gn(s, cur, _Point(self, staged, meas_delta=meas_delta, Pw=Pw), outs, max_iter, tol)
 
     def resjac(self, X, U, Y, PAR=None, stream=None):
         """Per-node defects W (B,P,n) and dynamics Jacobians F (B,P,n,n), per-row
@@ -528,7 +550,7 @@ class BatchSolver:
                  Pw=None):
         """GN normal equations at X: H (B,dp,dp), g (B,dp), cost (B) -- dense, node-major
         (row j*n + c; padding nodes last) on both paths.  The large-system path runs the
-        solve's own k_big_resid + k_big_assemble over a workspace (mhe_assemble_kkt_ws) and
+        solve's own k_big_resid + k_big_assemble over a workspace (mhe_assemble_at) and
         copies H out of their component-major tiles.  A bordered problem (n_extra / n_eq
         > 0) returns the KKT system of kkt_dim rows instead (H_xz, H_zz, the constraint
         rows; g = [g_x; g_z; C v - r]) at (X, Z).  ``Rw`` / ``meas_delta`` / ``Pw`` as for solve():
@@ -539,7 +561,8 @@ class BatchSolver:
         if self.fused_general:
             return self.sibling().assemble(X, U, Y, PAR, x0, stream, status_out, Z, Rw, meas_delta, Pw)
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
+            staged = self._inputs(X, U, Y, PAR, x0)
+            B = staged.B
             Z_t = None
             if self.n_extra:
                 Z_t = _dev(np.zeros((B, self.n_extra)) if Z is None else Z, self.device, (B, self.n_extra))
@@ -548,38 +571,15 @@ class BatchSolver:
             g = torch.empty((B, dk), dtype=torch.float64, device=self.device)
             cost = torch.empty(B, dtype=torch.float64, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
-            # the large-system workspace is streamed in chunks like solve()'s (C5: 0.28 GB per
-            # trajectory), the outputs written in place at each chunk's offset
-            chunk = max(1, self._chunk(B, s))
-            ws, nb = self._workspace(chunk, s)
-            P, n, M = self.P, self.n, self.M
-            Rw_t, rstr = self._rw(Rw, B)
-            md_t, mstr = self._md(meas_delta, B)
-            Pw_t, wstr = self._pw(Pw, B)
-            for lo in range(0, B, chunk):
-                c = min(chunk, B - lo)
-                if Rw_t is not None or md_t is not None or Pw_t is not None:
-                    a = _lib.MheSolveArgs()
-                    a.batch = c
-                    a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, self.n_extra)
-                    a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
-                    a.Y = _at(Y_t, lo, M * self.p)
-                    a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
-                    a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
-                    a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
-                    a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
-                    a.x0 = _at(x0_t, lo, n)
-                    a.workspace, a.workspace_bytes = _ptr(ws), nb
-                    rc = self.lib.mhe_assemble_at(self.dims, _ptr(self.cbuf), ctypes.byref(a), _at(H, lo, dk * dk),
-                                                  _at(g, lo, dk), _at(cost, lo, 1), _at(status, lo, 1, 4), _handle(s))
-                    _lib.check(rc, "mhe_assemble_at")
-                    continue
-                rc = self.lib.mhe_assemble_kkt_ws(
-                    self.dims, _ptr(self.cbuf), c, _at(X, lo, P * n), _at(Z_t, lo, self.n_extra), _at(U_t, lo, ustr),
-                    ustr, _at(Y_t, lo, M * self.p), _at(PAR_t, lo, pstr), pstr, _at(x0_t, lo, n), _at(H, lo, dk * dk),
-                    _at(g, lo, dk), _at(cost, lo, 1), _at(status, lo, 1, 4), _ptr(ws), nb, _handle(s))
-                _lib.check(rc, "mhe_assemble_kkt_ws")
-            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, H, g, cost, status, ws)
+            # the large-system workspace is streamed in chunks like solve()'s (C5: 0.28 GB per trajectory)
+            _, ws, nb, spans = self._chunks(B, s)
+            pt = _Point(self, staged, Z_t, None, Rw, meas_delta, Pw)
+            for lo, c in spans:
+                rc = self.lib.mhe_assemble_at(self.dims, _ptr(self.cbuf), ctypes.byref(pt.args(lo, c, ws, nb)),
+                                              _at(H, lo, dk * dk), _at(g, lo, dk), _at(cost, lo, 1),
+                                              _at(status, lo, 1, 4), _handle(s))
+                _lib.check(rc, "mhe_assemble_at")
+            keep_alive(s, cur, *pt.tensors, H, g, cost, status, ws)
         if status_out:
             return H, g, cost, status
         return H, g, cost
@@ -629,42 +629,27 @@ class BatchSolver:
         if Phi.shape[0] != 1:
             raise ValueError(f"arrival() takes exactly one query time, got {Phi.shape[0]}")
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
-            Rw_t, rstr = self._rw(Rw, B)
-            md_t, mstr = self._md(meas_delta, B)
-            Pw_t, wstr = self._pw(Pw, B)
+            staged = self._inputs(X, U, Y, PAR, x0)
+            B, n = staged.B, self.n
+            pt = _Point(self, staged, self._z(Z, B), None, Rw, meas_delta, Pw)
             phi = _dev(Phi, self.device)
-            Z_t = self._z(Z, B)
             call, cname = ((self.lib.mhe_kkt_arrival, "mhe_kkt_arrival") if self.general else
                            (self.lib.mhe_arrival, "mhe_arrival"))
-            n, P, M = self.n, self.P, self.M
             f64 = dict(dtype=torch.float64, device=self.device)
             x_arr = torch.empty((B, n), **f64)
             Pw_arr = torch.empty((B, n, n), **f64)
             cov = torch.empty((B, n, n), **f64) if with_cov else None
             status = torch.empty(B, dtype=torch.int32, device=self.device)
-            chunk = max(1, self._chunk(B, s))  # streamed in chunks like covariance()
-            ws, nb = self._workspace(chunk, s)
+            chunk, ws, nb, spans = self._chunks(B, s)  # streamed in chunks like covariance()
             sb = (self.lib.mhe_kkt_cov_scratch_bytes(self.dims, chunk, 1) if self.general else
                   self.lib.mhe_arrival_scratch_bytes(self.dims, chunk))
             scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
-            for lo in range(0, B, chunk):
-                a = _lib.MheSolveArgs()
-                a.batch = min(chunk, B - lo)
-                a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, self.n_extra)
-                a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
-                a.Y = _at(Y_t, lo, M * self.p)
-                a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
-                a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
-                a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
-                a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
-                a.x0 = _at(x0_t, lo, n)
-                a.workspace, a.workspace_bytes = _ptr(ws), nb
-                rc = call(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(phi), _at(x_arr, lo, n),
-                          _at(Pw_arr, lo, n * n), _at(cov, lo, n * n), _at(status, lo, 1, 4), _ptr(scratch), sb, _handle(s))
+            for lo, c in spans:
+                rc = call(self.dims, _ptr(self.cbuf), ctypes.byref(pt.args(lo, c, ws, nb)), _ptr(phi),
+                          _at(x_arr, lo, n), _at(Pw_arr, lo, n * n), _at(cov, lo, n * n), _at(status, lo, 1, 4),
+                          _ptr(scratch), sb, _handle(s))
                 _lib.check(rc, cname)
-            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, phi, x_arr, Pw_arr, cov, status, ws,
-                       scratch)
+            keep_alive(s, cur, *pt.tensors, phi, x_arr, Pw_arr, cov, status, ws, scratch)
         if with_cov:
             return x_arr, Pw_arr, status, cov
         return x_arr, Pw_arr, status
@@ -696,48 +681,33 @@ class BatchSolver:
         if Tq == 0:
             raise ValueError("at least one query time")
         with launch_stream(stream, self.device, (self._built,)) as (s, cur):
-            X, B, U_t, ustr, Y_t, PAR_t, pstr, x0_t = self._inputs(X, U, Y, PAR, x0)
-            Rw_t, rstr = self._rw(Rw, B)
-            md_t, mstr = self._md(meas_delta, B)
-            Pw_t, wstr = self._pw(Pw, B)
+            staged = self._inputs(X, U, Y, PAR, x0)
+            B, n, nz = staged.B, self.n, self.n_extra
+            pt = _Point(self, staged, self._z(Z, B) if self.general else None, None, Rw, meas_delta, Pw)
             PhiQ = _dev(Phi, self.device)
-            Z_t = self._z(Z, B) if self.general else None
-            n, P, M, nz = self.n, self.P, self.M, self.n_extra
             covz = None
             if self.general and with_extra and nz:
                 covz = torch.empty((B, nz, nz), dtype=torch.float64, device=self.device)
             cov = torch.empty((B, Tq, n, n), dtype=torch.float64, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
             # the large-system workspace and the query columns' scratch are streamed in
-            # chunks like solve()'s, the outputs written in place at each chunk's offset
-            chunk = max(1, self._chunk(B, s))
-            ws, nb = self._workspace(chunk, s)
+            # chunks like solve()'s
+            chunk, ws, nb, spans = self._chunks(B, s)
             sb = (self.lib.mhe_kkt_cov_scratch_bytes if self.general else self.lib.mhe_cov_scratch_bytes)(
                 self.dims, chunk, Tq)
             scratch = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
-            for lo in range(0, B, chunk):
-                a = _lib.MheSolveArgs()
-                a.batch = min(chunk, B - lo)
-                a.X0, a.Z0 = _at(X, lo, P * n), _at(Z_t, lo, nz)
-                a.U, a.u_bstride = _at(U_t, lo, ustr), ustr
-                a.Y = _at(Y_t, lo, M * self.p)
-                a.PAR, a.par_bstride = _at(PAR_t, lo, pstr), pstr
-                a.Rw, a.rw_bstride = _at(Rw_t, lo, rstr), rstr
-                a.meas_delta, a.md_bstride = _at(md_t, lo, mstr), mstr
-                a.Pw, a.pw_bstride = _at(Pw_t, lo, wstr), wstr
-                a.x0 = _at(x0_t, lo, n)
-                a.workspace, a.workspace_bytes = _ptr(ws), nb
+            for lo, c in spans:
+                a = ctypes.byref(pt.args(lo, c, ws, nb))
                 if self.general:
-                    rc = self.lib.mhe_kkt_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
-                                              _at(cov, lo, Tq * n * n), _at(covz, lo, nz * nz), _at(status, lo, 1, 4),
-                                              _ptr(scratch), sb, _handle(s))
+                    rc = self.lib.mhe_kkt_cov(self.dims, _ptr(self.cbuf), a, _ptr(PhiQ), Tq, _at(cov, lo, Tq * n * n),
+                                              _at(covz, lo, nz * nz), _at(status, lo, 1, 4), _ptr(scratch), sb,
+                                              _handle(s))
                     _lib.check(rc, "mhe_kkt_cov")
                     continue
-                rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), ctypes.byref(a), _ptr(PhiQ), Tq,
-                                            _at(cov, lo, Tq * n * n), _at(status, lo, 1, 4), _ptr(scratch), sb,
-                                            _handle(s))
+                rc = self.lib.mhe_state_cov(self.dims, _ptr(self.cbuf), a, _ptr(PhiQ), Tq, _at(cov, lo, Tq * n * n),
+                                            _at(status, lo, 1, 4), _ptr(scratch), sb, _handle(s))
                 _lib.check(rc, "mhe_state_cov")
-            keep_alive(s, cur, X, Z_t, U_t, Y_t, PAR_t, Rw_t, md_t, Pw_t, x0_t, PhiQ, cov, covz, status, ws, scratch)
+            keep_alive(s, cur, *pt.tensors, PhiQ, cov, covz, status, ws, scratch)
         if with_extra:
             return cov, covz, status
         return cov, status
@@ -760,10 +730,8 @@ class BatchSolver:
                 raise ValueError(f"H must be (B,{dk},{dk}) and g (B,{dk})")
             delta = torch.empty((B, dk), dtype=torch.float64, device=self.device)
             status = torch.empty(B, dtype=torch.int32, device=self.device)
-            chunk = max(1, self._chunk(B, s))
-            ws, nb = self._workspace(chunk, s)
-            for lo in range(0, B, chunk):
-                c = min(chunk, B - lo)
+            _, ws, nb, spans = self._chunks(B, s)
+            for lo, c in spans:
                 rc = self.lib.mhe_chol_solve_ws(self.dims, _ptr(self.cbuf), c, _at(H, lo, dk * dk), _at(g, lo, dk),
                                                 _at(delta, lo, dk), _at(status, lo, 1, 4), _ptr(ws), nb, _handle(s))
                 _lib.check(rc, "mhe_chol_solve_ws")

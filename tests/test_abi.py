@@ -51,6 +51,7 @@ def test_set_option_is_explicit_and_bounded():
     assert lib.mhe_set_option(_lib.OPT_DEBUG_SMEM_PAD, -5) == -1
     assert lib.mhe_set_option(77, 1) == -1
     src = open(os.path.join(ROOT, "nlp-filter_amd", "csrc", "mhe_core.h")).read()
+    src += open(os.path.join(ROOT, "nlp-filter_amd", "csrc", "mhe_launch.h")).read()  # the host launch layer
     src += open(os.path.join(ROOT, "nlp-filter_amd", "csrc", "mhe_gn.hip")).read()
     assert "getenv" not in src
 

@@ -37,8 +37,8 @@ def split(text):
         if ".amdgpu_metadata" in line:
             break               # the YAML notes repeat the descriptors; no code follows
         line = re.sub(r"\s*;.*$", "", line).rstrip()
-        if not line:
-            continue
+        if not line or re.match(r"\s*\.type\s+__hip_cuid_", line):
+            continue            # (the per-unit source hash's .type line trails the symbol before it)
         m = re.match(r"\s*\.amdhsa_kernel (\S+)", line)
         if m:
             kd = m.group(1)

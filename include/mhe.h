@@ -662,6 +662,36 @@ int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* 
                 const double* Q, const double* R, int64_t r_bstride, int64_t r_sstride,
                 double* mu_hist, double* S_hist, int32_t* status, void* stream);
 
+/*
+ * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
+ * (added to ABI v11; no existing struct or function changed).  One filter per lane;
+ * a filter's result does not depend on the batch or on its place in it.
+ * For k = steps-2 .. 0, with (x-, G) = f(mu_k, u_{k+1}) and S- = G S_k G^T + Q recomputed
+ * by the forward pass's own dynamics functor:
+ *   C = S_k G^T (S-)^-1,  mu_s[k] = mu_k + C (mu_s[k+1] - x-),  S_s[k] = S_k + C (S_s[k+1] - S-) C^T
+ * and mu_s / S_s of the last step are the filtered ones.  S- is factored by Cholesky.
+ * Of dims this call reads struct_size, n, m, dyn_model, dt, dyn_par, hist_batch_inner (the
+ * layout of mu_hist, S_hist, mu_s and S_s alike) and in_batch_inner (the layout of U);
+ * pmax, q, meas_model and r_diag are not read: measurements and R do not enter.
+ *   mu_hist, S_hist  filtered histories; only the upper triangle of S_hist is read
+ *   U, u_bstride, Q  as mhe_ekf_run
+ *   mu0 (B,n), S0 (B,n,n)      optional: the prior the filter started from
+ *   mu_s, S_s        smoothed histories, S_s bitwise symmetric.  They may alias mu_hist /
+ *                    S_hist (in place): every lane reads a step before it writes it
+ *   mu0_s (B,n), S0_s (B,n,n)  optional (need mu0 and S0): the smoothed prior, one more
+ *                    step of the recursion from (mu0, S0) with u_0
+ *   status (B, optional): 0 ok; 1 a pivot of S- was not positive and finite, or the history
+ *                    held a non-finite value: that filter's outputs are NaN from the failing
+ *                    step down to step 0 (and its smoothed prior); the steps above it and
+ *                    every other filter are untouched.
+ * Stream-ordered: no host synchronisation, no allocation.  Returns MHE_OK or MHE_ERR_*
+ * (batch == 0 or steps == 0: MHE_OK, nothing is read).
+ */
+int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const double* mu_hist,
+                   const double* S_hist, const double* U, int64_t u_bstride, const double* Q,
+                   const double* mu0, const double* S0, double* mu_s, double* S_s, double* mu0_s,
+                   double* S0_s, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------------
  * Batched GNSS least-squares fixes (the MHE initialiser).
  * Replaces utils/leastsquares.py:19-42 (iterativeLeastSquares),

@@ -507,7 +507,282 @@ int launch(EkfArgs& a, hipStream_t st, bool r_diag) {
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
+// ---------------------------------------------------------------- fixed-interval smoother
+// Rauch-Tung-Striebel backward pass over a filtered history (mu_k, S_k), one filter per
+// lane as k_ekf_lane: no LDS, no barriers, no cross-lane traffic.  Carrying the smoothed
+// (xs, Ss) of step k+1, step k recomputes the forward's prediction from its own output,
+//   (x-, G) = DYN::step(mu_k, u_{k+1}),  S- = G S_k G^T + Q   (k_ekf_lane's predict, term by term)
+// factors S- = L L^T (true sqrt and division: the result is user-facing) and, with
+// A = G S_k and M = S-^-1 A (= C_k^T, two triangular solves per column, in place in A),
+//   xs_k = mu_k + M^T (xs_{k+1} - x-),   Ss_k = S_k + M^T (Ss_{k+1} - S-) M.
+// Measurements and R do not enter.  Registers: S_k, S- / L and the carry are upper triangles
+// (LaneS); G is dead once A and S- are formed, L overwrites S-, D = Ss_{k+1} - S- overwrites
+// the carry, M overwrites A and the triangle of S_k is the accumulator of Ss_k.  The inputs of
+// step k-1 do not depend on the recursion and are loaded before step k's arithmetic.
+// The prior (mu0, S0), when asked for, is one more step of the same loop at k = -1 with u_0.
+struct RtsArgs {
+  int batch, steps;
+  double dt;
+  double dp[8];
+  const double* mu_hist;
+  const double* S_hist;
+  const double* U;
+  long long u_bstride, es;  // as EkfArgs
+  const double* Q;
+  const double* mu0;        // (B, n) / (B, n, n), batch outermost; read only when a smoothed prior is asked for
+  const double* S0;
+  double* mu_s;             // may alias mu_hist / S_hist: a lane reads step k-1 before it writes step k
+  double* S_s;
+  double* mu0_s;
+  double* S0_s;
+  int hist_bi;
+  int* status;
+};
+
+// where step k's w-entry record of filter b starts and the stride between its entries;
+// k = -1 is the prior's (B, w) array
+struct RtsRec {
+  long long off, es;
+};
+__device__ __forceinline__ RtsRec rts_rec(const RtsArgs& a, int b, int k, int w) {
+  if (k < 0) return {(long long)b * w, 1};
+  if (a.hist_bi) return {(long long)k * w * a.batch + b, a.batch};
+  return {((long long)b * a.steps + k) * w, 1};
+}
+
+template <class DYN>
+struct RtsIn {
+  double mu[DYN::n], S[LaneS<DYN::n>::size], u[DYN::m > 0 ? DYN::m : 1];
+};
+
+// (mu_k, upper triangle of S_k, u_{k+1}) of filter b; k = -1 reads the prior.  The last
+// step has no u_{k+1} (with_u = false: U holds `steps` controls).
+template <class DYN, bool with_u = true>
+__device__ __forceinline__ void rts_load(const RtsArgs& a, int b, int k, RtsIn<DYN>& in) {
+  constexpr int n = DYN::n, m = DYN::m;
+  using LS = LaneS<n>;
+  const RtsRec rm = rts_rec(a, b, k, n), rs = rts_rec(a, b, k, n * n);
+  const double* pm = (k < 0 ? a.mu0 : a.mu_hist) + rm.off;
+  const double* ps = (k < 0 ? a.S0 : a.S_hist) + rs.off;
+#pragma unroll
+  for (int c = 0; c < n; ++c) in.mu[c] = pm[c * rm.es];
+#pragma unroll
+  for (int r = 0; r < n; ++r)
+#pragma unroll
+    for (int c = r; c < n; ++c) in.S[LS::at(r, c)] = ps[(r * n + c) * rs.es];
+  if (with_u) {
+#pragma unroll
+    for (int c = 0; c < m; ++c) in.u[c] = a.U[(long long)b * a.u_bstride + ((long long)(k + 1) * m + c) * a.es];
+  }
+}
+
+// smoothed step k: S_s(r, c) and S_s(c, r) from one register, so the output is bitwise symmetric
+template <int n>
+__device__ __forceinline__ void rts_store(const RtsArgs& a, int b, int k, const double* xs, const double* Ss) {
+  using LS = LaneS<n>;
+  double* pm = k < 0 ? a.mu0_s : a.mu_s;
+  double* ps = k < 0 ? a.S0_s : a.S_s;
+  const RtsRec rm = rts_rec(a, b, k, n), rs = rts_rec(a, b, k, n * n);
+  if (pm) {
+#pragma unroll
+    for (int c = 0; c < n; ++c) pm[rm.off + c * rm.es] = xs[c];
+  }
+  if (ps) {
+#pragma unroll
+    for (int r = 0; r < n; ++r)
+#pragma unroll
+      for (int c = 0; c < n; ++c) ps[rs.off + (r * n + c) * rs.es] = Ss[LS::at(r, c)];
+  }
+}
+
+// a failed filter's outputs are NaN from the failing step down; a non-finite entry (a NaN or
+// an infinity met in the history) is a failure as well
+template <int n>
+__device__ __forceinline__ bool rts_finite(const double* xs, const double* Ss) {
+  double t = 0.0;
+#pragma unroll
+  for (int c = 0; c < n; ++c) t += fabs(xs[c]);
+#pragma unroll
+  for (int i = 0; i < LaneS<n>::size; ++i) t += fabs(Ss[i]);
+  return t < INFINITY;
+}
+
+template <class DYN>
+__global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a) {
+  constexpr int n = DYN::n;
+  using LS = LaneS<n>;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.batch) return;  // no barriers below
+  const int kmin = (a.mu0_s || a.S0_s) ? -1 : 0;
+  bool bad = false;
+  double xs[n], Ss[LS::size];
+  {  // k = T-1: the smoothed values are the filtered ones
+    RtsIn<DYN> last;
+    rts_load<DYN, false>(a, b, a.steps - 1, last);
+#pragma unroll
+    for (int c = 0; c < n; ++c) xs[c] = last.mu[c];
+#pragma unroll
+    for (int i = 0; i < LS::size; ++i) Ss[i] = last.S[i];
+  }
+  RtsIn<DYN> in = {};
+  if (a.steps - 2 >= kmin) rts_load<DYN>(a, b, a.steps - 2, in);  // else no step follows (and U has no u_{k+1})
+  if (!rts_finite<n>(xs, Ss)) {
+    bad = true;
+#pragma unroll
+    for (int c = 0; c < n; ++c) xs[c] = NAN;
+#pragma unroll
+    for (int i = 0; i < LS::size; ++i) Ss[i] = NAN;
+  }
+  rts_store<n>(a, b, a.steps - 1, xs, Ss);
+  for (int k = a.steps - 2; k >= kmin; --k) {
+    // step k-1's inputs do not depend on the recursion: issued ahead of this step's
+    // arithmetic, they arrive under it (the last step re-reads its own)
+    RtsIn<DYN> nx;
+    rts_load<DYN>(a, b, max(k - 1, kmin), nx);
+    double xp[n], A[n * n], L[LS::size];
+    {
+      double G[n * n];
+      DYN::step(in.mu, in.u, a.dt, a.dp, xp, G);
+#pragma unroll
+      for (int c = 0; c < n; ++c) {  // row c of A = G S_k, then column c of S- = A G^T + Q
+#pragma unroll
+        for (int l = 0; l < n; ++l) {
+          double acc = 0.0;
+#pragma unroll
+          for (int kk = 0; kk < n; ++kk)
+            if (DYN::gnz(c, kk)) acc += in.S[LS::at(l, kk)] * G[c * n + kk];
+          A[c * n + l] = acc;
+        }
+#pragma unroll
+        for (int r = 0; r <= c; ++r) {
+          double acc = 0.0;
+#pragma unroll
+          for (int l = 0; l < n; ++l)
+            if (DYN::gnz(r, l)) acc += G[r * n + l] * A[c * n + l];
+          L[LS::at(r, c)] = acc + a.Q[r * n + c];
+        }
+      }
+    }
+    double d[n];
+#pragma unroll
+    for (int c = 0; c < n; ++c) d[c] = xs[c] - xp[c];
+#pragma unroll
+    for (int i = 0; i < LS::size; ++i) Ss[i] -= L[i];  // D = Ss_{k+1} - S-
+    // S- = L L^T in place (L(i, j), i > j, in the slot of S-(j, i)); the diagonal slot keeps 1 / L(j, j)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double piv = L[LS::at(j, j)];
+#pragma unroll
+      for (int t = 0; t < j; ++t) piv -= L[LS::at(j, t)] * L[LS::at(j, t)];
+      bad |= !(piv > 0.0 && piv < INFINITY);
+      const double inv = 1.0 / sqrt(piv);
+      L[LS::at(j, j)] = inv;
+#pragma unroll
+      for (int i = j + 1; i < n; ++i) {
+        double v = L[LS::at(i, j)];
+#pragma unroll
+        for (int t = 0; t < j; ++t) v -= L[LS::at(i, t)] * L[LS::at(j, t)];
+        L[LS::at(i, j)] = v * inv;
+      }
+    }
+    // M = S-^-1 A, column by column in place: L y = A(:, c), L^T m = y
+#pragma unroll
+    for (int c = 0; c < n; ++c) {
+#pragma unroll
+      for (int r = 0; r < n; ++r) {
+        double v = A[r * n + c];
+#pragma unroll
+        for (int t = 0; t < r; ++t) v -= L[LS::at(r, t)] * A[t * n + c];
+        A[r * n + c] = v * L[LS::at(r, r)];
+      }
+#pragma unroll
+      for (int r = n - 1; r >= 0; --r) {
+        double v = A[r * n + c];
+#pragma unroll
+        for (int t = r + 1; t < n; ++t) v -= L[LS::at(t, r)] * A[t * n + c];
+        A[r * n + c] = v * L[LS::at(r, r)];
+      }
+    }
+    // xs_k = mu_k + M^T d;  Ss_k = S_k + M^T D M, accumulated on S_k's triangle
+#pragma unroll
+    for (int c = 0; c < n; ++c) {
+      double acc = 0.0;
+#pragma unroll
+      for (int r = 0; r < n; ++r) acc += A[r * n + c] * d[r];
+      xs[c] = in.mu[c] + acc;
+      double e[n];  // D M(:, c)
+#pragma unroll
+      for (int l = 0; l < n; ++l) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < n; ++j) s += Ss[LS::at(l, j)] * A[j * n + c];
+        e[l] = s;
+      }
+#pragma unroll
+      for (int r = 0; r <= c; ++r) {
+        double s = 0.0;
+#pragma unroll
+        for (int l = 0; l < n; ++l) s += A[l * n + r] * e[l];
+        in.S[LS::at(r, c)] += s;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < LS::size; ++i) Ss[i] = in.S[i];
+    if (bad || !rts_finite<n>(xs, Ss)) {
+      bad = true;
+#pragma unroll
+      for (int c = 0; c < n; ++c) xs[c] = NAN;
+#pragma unroll
+      for (int i = 0; i < LS::size; ++i) Ss[i] = NAN;
+    }
+    rts_store<n>(a, b, k, xs, Ss);
+    in = nx;
+  }
+  if (a.status) a.status[b] = bad ? 1 : 0;
+}
+
+template <class DYN>
+int launch_rts(const RtsArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL((k_ekf_rts<DYN>), dim3((a.batch + 255) / 256), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
 }  // namespace mhe_ekf
+
+extern "C" int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const double* mu_hist,
+                              const double* S_hist, const double* U, int64_t u_bstride, const double* Q,
+                              const double* mu0, const double* S0, double* mu_s, double* S_s, double* mu0_s,
+                              double* S0_s, int32_t* status, void* stream) {
+  using namespace mhe_ekf;
+  if (!dims) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (batch < 0 || steps < 0) return MHE_ERR_DIMS;
+  if (batch == 0 || steps == 0) return MHE_OK;
+  int (*run)(const RtsArgs&, hipStream_t) = nullptr;
+  if (dims->dyn_model == MHE_EKF_DYN_GNSS_POS_AND_BIAS) {
+    if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
+    run = launch_rts<EkfGnssPosAndBias>;
+  } else if (dims->dyn_model == MHE_EKF_DYN_DISCRETE_VEHICLE) {
+    if (dims->n != 9 || dims->m != 2) return MHE_ERR_MODEL;
+    if (!(dims->dyn_par[2] != 0.0 && dims->dyn_par[5] != 0.0)) return MHE_ERR_DIMS;  // M, I_Z unset
+    run = launch_rts<EkfDiscreteVehicle>;
+  } else {
+    return MHE_ERR_MODEL;
+  }
+  if (!mu_hist || !S_hist || !U || !Q || !mu_s || !S_s) return MHE_ERR_NULL;
+  if ((mu0_s || S0_s) && (!mu0 || !S0)) return MHE_ERR_NULL;
+  RtsArgs a = {};
+  a.batch = batch; a.steps = steps; a.dt = dims->dt;
+  for (int i = 0; i < 8; ++i) a.dp[i] = dims->dyn_par[i];
+  a.mu_hist = mu_hist; a.S_hist = S_hist; a.U = U; a.u_bstride = u_bstride; a.es = 1; a.Q = Q;
+  a.mu0 = mu0; a.S0 = S0; a.mu_s = mu_s; a.S_s = S_s; a.mu0_s = mu0_s; a.S0_s = S0_s; a.status = status;
+  a.hist_bi = dims->hist_batch_inner != 0;
+  if (dims->in_batch_inner) {  // U (steps, m, B)
+    a.es = batch;
+    a.u_bstride = 1;
+  }
+  return run(a, (hipStream_t)stream);
+}
 
 extern "C" int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* mu, double* S,
                            const double* U, int64_t u_bstride, const double* Z, int64_t z_bstride, const int32_t* nz,

@@ -5,7 +5,9 @@ dyn_func_params, meas_func, meas_func_params)`` keep the reference signatures
 and semantics (utils/ekf.py:11-38): ``mu`` / ``S`` are NumPy arrays replaced by
 each update; ``z=None`` predicts only.  Each update is one launch of
 ``mhe_ekf_run`` (csrc/mhe_ekf.hip); ``run_batch`` runs many independent filter
-instances over many steps in a single launch (the GPU-shaped entry point).
+instances over many steps in a single launch (the GPU-shaped entry point), and
+``smooth_batch`` is the fixed-interval (RTS) smoother over the history it returns
+(``mhe_ekf_smooth``).
 Plug-ins are resolved by name (``utils.gnss.EKF_DYN`` / ``EKF_MEAS``: the
 utils/gnss.py models and autonomous-car.py's own ``discrete_vehicle_dynamics`` /
 ``vehicle_sensors_model``); a user's callable is then evaluated at seeded points
@@ -87,40 +89,58 @@ def verify(dyn_func, meas_func, dyn_params):
     other constants must not silently get the built-in device functor.  Strings and this
     package's own functions pass without evaluation; results are cached per callable
     and parameter values."""
-    (_, n, m), (_, _, q) = models(dyn_func, meas_func)
-    for fn, kind in ((dyn_func, "dyn"), (meas_func, "meas")):
-        if isinstance(fn, str):
-            continue
-        twin = _twin(_name(fn))
-        if fn is twin:
-            continue
-        key = (id(fn), kind, _params_key(dyn_params) if kind == "dyn" else ())
-        if _VERIFIED.get(key) is fn:
-            continue
-        rng = np.random.default_rng(20262)
-        for _ in range(4):
-            x = rng.normal(size=n) * 3.0
-            if n == 9:
-                x[3] = 5.0 + abs(x[3])   # forward speed away from the tyre model's pole at vx = 0
-            try:
-                if kind == "dyn":
-                    u = rng.normal(size=m)
-                    got = fn(x.copy(), u, params=dyn_params, jac=True)
-                    ref = twin(x.copy(), u, params=dyn_params, jac=True)
-                else:
-                    p = {"sat_pos": rng.normal(size=(4, 3)) * 2.0e4}
-                    got = fn(x.copy(), params=p, jac=True)
-                    ref = twin(x.copy(), params=p, jac=True)
-            except UnsupportedPlugin:
-                raise
-            except Exception as e:
-                raise UnsupportedPlugin(f"EKF plug-in {_name(fn)!r} could not be evaluated to verify it matches "
-                                        f"the device functor: {type(e).__name__}: {e}") from e
-            if not (_close(got[0], ref[0]) and _close(got[1], ref[1])):
-                raise UnsupportedPlugin(f"EKF plug-in {_name(fn)!r} is not the registered {_name(fn)}: its values "
-                                        "or Jacobian differ from the device functor's (same name, different math "
-                                        "or constants)")
-        _VERIFIED[key] = fn
+    (_, n, m), _ = models(dyn_func, meas_func)
+    _verify_one(dyn_func, "dyn", n, m, dyn_params)
+    _verify_one(meas_func, "meas", n, m, dyn_params)
+
+
+def dynamics(dyn_func):
+    """(id, n, m) of a dynamics plug-in by name -- the dynamics half of ``models``."""
+    dn = _name(dyn_func)
+    if dn not in _gnss.EKF_DYN:
+        raise UnsupportedPlugin(f"EKF dynamics plug-in {dn!r} has no HIP functor; registered: {sorted(_gnss.EKF_DYN)}")
+    return _gnss.EKF_DYN[dn]
+
+
+def verify_dynamics(dyn_func, dyn_params):
+    """The dynamics half of ``verify`` (the smoother has no measurement model)."""
+    _, n, m = dynamics(dyn_func)
+    _verify_one(dyn_func, "dyn", n, m, dyn_params)
+
+
+def _verify_one(fn, kind, n, m, dyn_params):
+    if isinstance(fn, str):
+        return
+    twin = _twin(_name(fn))
+    if fn is twin:
+        return
+    key = (id(fn), kind, _params_key(dyn_params) if kind == "dyn" else ())
+    if _VERIFIED.get(key) is fn:
+        return
+    rng = np.random.default_rng(20262)
+    for _ in range(4):
+        x = rng.normal(size=n) * 3.0
+        if n == 9:
+            x[3] = 5.0 + abs(x[3])   # forward speed away from the tyre model's pole at vx = 0
+        try:
+            if kind == "dyn":
+                u = rng.normal(size=m)
+                got = fn(x.copy(), u, params=dyn_params, jac=True)
+                ref = twin(x.copy(), u, params=dyn_params, jac=True)
+            else:
+                p = {"sat_pos": rng.normal(size=(4, 3)) * 2.0e4}
+                got = fn(x.copy(), params=p, jac=True)
+                ref = twin(x.copy(), params=p, jac=True)
+        except UnsupportedPlugin:
+            raise
+        except Exception as e:
+            raise UnsupportedPlugin(f"EKF plug-in {_name(fn)!r} could not be evaluated to verify it matches "
+                                    f"the device functor: {type(e).__name__}: {e}") from e
+        if not (_close(got[0], ref[0]) and _close(got[1], ref[1])):
+            raise UnsupportedPlugin(f"EKF plug-in {_name(fn)!r} is not the registered {_name(fn)}: its values "
+                                    "or Jacobian differ from the device functor's (same name, different math "
+                                    "or constants)")
+    _VERIFIED[key] = fn
 
 
 def _ptr(t):
@@ -228,6 +248,84 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     mh = mh_st.permute(2, 0, 1) if keep_history else None
     Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
     return mh, Sh, mu, S, st
+
+
+def _hist_storage(t, w):
+    """The storage a (B, T, *w) history tensor hands to the kernel and whether it is
+    batch-innermost: run_batch's views (permuted (T, *w, B) storage) pass as they are, no
+    copy; every other layout is made contiguous batch-outermost."""
+    if t.dim() == 2 + len(w) and t.shape[0] > 0:
+        perm = tuple(range(1, t.dim())) + (0,)
+        if not t.is_contiguous() and t.permute(*perm).is_contiguous():
+            return t.permute(*perm), True
+    return t.contiguous(), False
+
+
+def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_params=None, inputs="batch_outer",
+                 device=None, stream=None):
+    """Fixed-interval (Rauch-Tung-Striebel) smoother over a filtered history, B filters
+    in one launch of ``mhe_ekf_smooth`` (one filter per lane).
+
+    mu_hist (B,T,n), S_hist (B,T,n,n): what run_batch returned (its batch-innermost views
+    go to the kernel without a copy; other layouts are copied to contiguous batch-outermost);
+    U (B,T,m) -- or (T,m,B) with inputs="batch_inner" -- and Q (n,n), dt, dyn_params: as
+    given to run_batch.  mu0 (B,n), S0 (B,n,n): optionally the prior the filter started
+    from; the smoothed prior is then returned too.
+    Returns (mu_s (B,T,n), S_s (B,T,n,n), status (B)) and, with a prior, also
+    (mu0_s (B,n), S0_s (B,n,n)).  status 1: a predicted covariance had no Cholesky factor or
+    the history held a non-finite value; that filter is NaN from the failing step down.
+
+    stream: as run_batch (mhe.streams)."""
+    import torch
+
+    from mhe.streams import keep_alive, launch_stream
+
+    did, n, m = dynamics(dyn_func)
+    if dyn_params is not None and "dt" in dyn_params:
+        dt = dyn_params["dt"]
+    if inputs not in ("batch_outer", "batch_inner"):
+        raise ValueError(f"unknown inputs layout {inputs!r}")
+    if (mu0 is None) != (S0 is None):
+        raise ValueError("smooth_batch: mu0 and S0 go together")
+    bi = inputs == "batch_inner"
+    shp = lambda a: tuple(a.shape)   # noqa: E731
+    if len(shp(mu_hist)) != 3 or len(shp(S_hist)) != 4:
+        raise ValueError("smooth_batch: mu_hist must be (B,T,n) and S_hist (B,T,n,n)")
+    B, T = shp(mu_hist)[:2]
+    if shp(mu_hist) != (B, T, n) or shp(S_hist) != (B, T, n, n) or shp(Q) != (n, n) \
+            or shp(U) != ((T, m, B) if bi else (B, T, m)) \
+            or (mu0 is not None and (shp(mu0) != (B, n) or shp(S0) != (B, n, n))):
+        raise ValueError("smooth_batch: inconsistent shapes")
+    verify_dynamics(dyn_func, dict(dyn_params or {}, dt=dt))
+    dp = dyn_par(dyn_func, dyn_params)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with launch_stream(stream, dev) as (s, cur):
+        def d(a):
+            return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=torch.float64, device=dev)
+
+        mh, mh_bi = _hist_storage(d(mu_hist), (n,))
+        Sh, Sh_bi = _hist_storage(d(S_hist), (n, n))
+        if mh_bi != Sh_bi:   # one layout flag covers both histories
+            mh, Sh, mh_bi = d(mu_hist).contiguous(), d(S_hist).contiguous(), False
+        Ut, Qt = d(U).contiguous(), d(Q).contiguous()
+        prior = mu0 is not None
+        m0, S0t = (d(mu0).contiguous(), d(S0).contiguous()) if prior else (None, None)
+        ms, Ss = torch.empty_like(mh), torch.empty_like(Sh)
+        m0s, S0s = (torch.empty_like(m0), torch.empty_like(S0t)) if prior else (None, None)
+        st = torch.empty(B, dtype=torch.int32, device=dev)
+        dims = _lib.MheEkfDims(n=n, m=m, dyn_model=did, dt=float(dt), hist_batch_inner=int(mh_bi),
+                               in_batch_inner=int(bi))
+        for i in range(8):
+            dims.dyn_par[i] = float(dp[i])
+        lib = _lib.load()
+        rc = lib.mhe_ekf_smooth(ctypes.byref(dims), B, T, _ptr(mh), _ptr(Sh), _ptr(Ut), T * m, _ptr(Qt), _ptr(m0),
+                                _ptr(S0t), _ptr(ms), _ptr(Ss), _ptr(m0s), _ptr(S0s), _ptr(st),
+                                ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ekf_smooth")
+        keep_alive(s, cur, mh, Sh, Ut, Qt, m0, S0t, ms, Ss, m0s, S0s, st)
+        if mh_bi:
+            ms, Ss = ms.permute(2, 0, 1), Ss.permute(3, 0, 1, 2)
+        return (ms, Ss, st, m0s, S0s) if prior else (ms, Ss, st)
 
 
 class EKF(object):

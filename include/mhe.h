@@ -663,6 +663,53 @@ int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* 
                 double* mu_hist, double* S_hist, int32_t* status, void* stream);
 
 /*
+ * Innovation gating and likelihood outputs (added within v11; no existing struct or function
+ * changed).  mhe_ekf_run_args takes mhe_ekf_run's arguments as a struct, plus:
+ *   gate    0: no screening.  > 0 (+inf allowed): row i (i < nz) of step k is screened out iff
+ *           d2_i > gate, d2_i = (z_i - h_i(mu-))^2 / (H_i S- H_i^T + R_ii) -- marginal and at
+ *           the prediction, so it depends neither on the row order nor on the other rows, and
+ *           is the same for r_diag = 1 and 0.  A NaN or non-positive denominator keeps the row
+ *           (status 1 then reports it).  The correction is the one above on the kept rows in
+ *           their order, with R's kept sub-block; rows keep their index (the bias row of
+ *           MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS is row nz-1 and is screened like any other);
+ *           a step whose rows are all screened out is predict-only.  NaN or negative: MHE_ERR_DIMS.
+ *   nis, loglik, rej   optional per-step outputs, (steps, B) with dims->hist_batch_inner, else
+ *           (B, steps): over the accepted rows a, nis = e_a^T P_a^-1 e_a and
+ *           loglik = -(nis + log det P_a + |a| log 2 pi) / 2; bit i of rej is set iff row i was
+ *           screened out (pmax <= 32: bit 31 is a row like any other).  A step with nz = 0, with
+ *           nz > pmax (status 2) or with every row screened out has nis = loglik = 0.
+ * gate == 0 with nis, loglik and rej all NULL runs exactly what mhe_ekf_run runs (which is this
+ * call with those four fields zero); refusals and return codes are mhe_ekf_run's, and a NULL or
+ * wrongly sized args struct is refused like dims.
+ */
+typedef struct mhe_ekf_args {
+  int32_t struct_size; /* = sizeof(mhe_ekf_args) */
+  int32_t batch, steps;
+  double* mu;
+  double* S;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const double* Q;
+  const double* R;
+  int64_t r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int32_t* status;
+  double gate;
+  double* nis;
+  double* loglik;
+  int32_t* rej;
+} mhe_ekf_args;
+
+int mhe_ekf_run_args(const mhe_ekf_dims* dims, const mhe_ekf_args* args, void* stream);
+
+/*
  * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
  * (added to ABI v11; no existing struct or function changed).  One filter per lane;
  * a filter's result does not depend on the batch or on its place in it.

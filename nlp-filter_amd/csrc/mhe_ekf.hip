@@ -120,6 +120,7 @@ template <bool with_bias>
 struct EkfMultiPseudorange {
   static constexpr int q = 3;
   static constexpr int lane_minw = with_bias ? 2 : 4;  // k_ekf_lane waves per SIMD (no spills)
+  static constexpr int lane_minw_gate = 2;  // the gated instances' own bound
   template <int n>
   __device__ static void row(const double* x, const double* par, int i, int nz, double& h, double* H) {
     if (with_bias && i == nz - 1) {
@@ -145,6 +146,7 @@ struct EkfMultiPseudorange {
 struct EkfVehicleSensors {
   static constexpr int q = 3;
   static constexpr int lane_minw = 2;
+  static constexpr int lane_minw_gate = 1;  // no scratch (spills go to AGPRs); 2 spills to scratch, 1.6x slower
   template <int n>
   __device__ static void row(const double* x, const double* par, int /*i*/, int /*nz*/, double& h, double* H) {
     const double l0 = par[0] - x[0], l1 = par[1] - x[1], l2 = par[2] - x[8];
@@ -184,6 +186,24 @@ struct EkfArgs {
   int* status;
 };
 
+// the gated instances (k_ekf<.., true>, k_ekf_lane<.., true>) take these as well; the others
+// keep the kernel arguments they had
+struct EkfGateArgs : EkfArgs {
+  double gate;     // screen threshold on d2_i = e_i^2 / (H_i S- H_i^T + R_ii); +inf: no screening
+  double* nis;     // per-step statistics, optional: (steps, B) with hist_bi, else (B, steps)
+  double* loglik;
+  int* rej;        // bit i: row i was screened out
+};
+template <bool GATE>
+struct KArgs { using type = EkfArgs; };
+template <>
+struct KArgs<true> { using type = EkfGateArgs; };
+
+constexpr double LOG_2PI = 1.8378770664093454836, LOG_2 = 0.69314718055994530942;
+
+// bits 0..rows-1 (rows <= 32)
+__device__ __forceinline__ unsigned row_bits(int rows) { return rows >= 32 ? 0xffffffffu : (1u << rows) - 1u; }
+
 // element (b, k, e) of a per-step history with `w` entries per step
 __device__ __forceinline__ size_t hist_at(const EkfArgs& a, int b, int k, int e, int w) {
   return a.hist_bi ? ((size_t)k * w + e) * a.batch + b : ((size_t)b * a.steps + k) * w + e;
@@ -203,8 +223,17 @@ struct WaveSmem {
                        T1 = H + MAXP * n, E = T1 + MAXP * n, Y = E + MAXP, W = Y + MAXP * n, total = W + MAXP;
 };
 
-template <class DYN, class MEAS>
-__global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
+// GATE (k_ekf and k_ekf_lane alike): innovation screening and the per-step statistics.
+// Row i of a step is screened out iff d2_i = e_i^2 / (H_i S- H_i^T + R_ii) > a.gate, with
+// e_i = z_i - h_i(mu-): marginal and at the prediction, so it depends neither on the row
+// order nor on the other rows, and both kernels decide alike.  A NaN or a non-positive
+// denominator keeps the row (status 1 then reports it).  The correction is the ungated one
+// on the kept rows in their order; rows keep their index (MEAS::row sees the original i, nz).
+// nis = e_a^T P_a^-1 e_a, loglik = -(nis + log det P_a + |a| log 2 pi) / 2 over the kept rows a
+// (both 0 when there is none), rej = the mask of screened rows.  GATE = false is the code
+// as it was: those instances serve every call without a gate or a statistics output.
+template <class DYN, class MEAS, bool GATE = false>
+__global__ __launch_bounds__(NWF * 64) void k_ekf(typename KArgs<GATE>::type a) {
   constexpr int n = DYN::n, m = DYN::m, q = MEAS::q;
   using WS = WaveSmem<n>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -291,16 +320,32 @@ __global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
 #pragma unroll
       for (int c = 0; c < n; ++c) t1[c] = row ? T1[i * n + c] : 0.0;
       if (row) e = E[i];
+      bool rowk = row;                // this lane holds a row of the sweep
+      unsigned km = 0xffffffffu;      // GATE: the kept rows (wave-uniform)
+      if constexpr (GATE) {
+        // lane i tests its own diagonal entry of P; a screened lane becomes a non-row with a
+        // zero row of [T1 | e], so its rows of Y and W below are zeros
+        double pd = 0.0;
+#pragma unroll
+        for (int j = 0; j < MAXP; ++j) pd = (j == i) ? p[j] : pd;
+        rowk = row && !(pd > 0.0 && e * e / pd > a.gate);
+        km = (unsigned)__ballot(rowk);
+        if (!rowk) {
+          e = 0.0;
+#pragma unroll
+          for (int c = 0; c < n; ++c) t1[c] = 0.0;
+        }
+      }
       double idg = 0.0;
       bool bad = false;
 #pragma unroll
       for (int c = 0; c < MAXP; ++c) {
-        if (c < nz) {
+        if (c < nz && (!GATE || ((km >> c) & 1u))) {
           const double piv = readlane_d(p[c], c);
           bad |= !(piv > 0.0 && piv < INFINITY);
           const double rs = 1.0 / sqrt(piv);
           const double qv = p[c] * rs;                 // L_ic (i > c)
-          const double mm = (i > c && row) ? qv * rs : 0.0;  // A'_ic / A'_cc
+          const double mm = (i > c && rowk) ? qv * rs : 0.0;  // A'_ic / A'_cc
           idg = (i == c) ? rs : idg;
 #pragma unroll
           for (int j = c + 1; j < MAXP; ++j)
@@ -315,6 +360,23 @@ __global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
 #pragma unroll
         for (int c = 0; c < n; ++c) Y[i * n + c] = t1[c] * idg;  // Y = L^-1 H S-
         W[i] = e * idg;                                         // w = L^-1 e
+      }
+      if constexpr (GATE) {
+        // nis = w^T w, log det P_a = -2 sum log(1 / L_ii): the rows sit in lanes 0..31
+        double s2 = rowk ? (e * idg) * (e * idg) : 0.0;
+        double lg = rowk ? log(idg) : 0.0;
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+          s2 += __shfl_xor(s2, off);
+          lg += __shfl_xor(lg, off);
+        }
+        if (lane == 0) {
+          const int cnt = __popc(km);
+          const size_t at = hist_at(a, b, k, 0, 1);
+          if (a.nis) a.nis[at] = cnt ? s2 : 0.0;
+          if (a.loglik) a.loglik[at] = cnt ? -0.5 * (s2 - 2.0 * lg + cnt * LOG_2PI) : 0.0;
+          if (a.rej) a.rej[at] = (int)(~km & row_bits(nz));
+        }
       }
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -334,6 +396,14 @@ __global__ __launch_bounds__(NWF * 64) void k_ekf(EkfArgs a) {
       if (nz > a.nmeas_rows_max) status = 2;
       for (int t = lane; t < n * n; t += 64) S[t] = SP[t];
       for (int t = lane; t < n; t += 64) mu[t] = MP[t];
+      if constexpr (GATE) {
+        if (lane == 0) {
+          const size_t at = hist_at(a, b, k, 0, 1);
+          if (a.nis) a.nis[at] = 0.0;
+          if (a.loglik) a.loglik[at] = 0.0;
+          if (a.rej) a.rej[at] = 0;
+        }
+      }
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -370,8 +440,14 @@ struct LaneS {
   }
 };
 
-template <class DYN, class MEAS>
-__global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
+// GATE: the screen needs S- before the first update touches S, so a screening pass over the
+// step's rows at (mu-, S-) leaves a keep mask in a register and the update pass skips the
+// masked rows.  No second copy of S is held; the update pass re-reads the rows' inputs.  With
+// a.gate = +inf (statistics only) the screening pass is skipped.  nis = sum e_i^2 / s_i and
+// log det P_a = sum log s_i = log prod s_i of the sequential updates.
+template <class DYN, class MEAS, bool GATE = false>
+__global__ __launch_bounds__(256, GATE ? MEAS::lane_minw_gate : MEAS::lane_minw)
+void k_ekf_lane(typename KArgs<GATE>::type a) {
   constexpr int n = DYN::n, m = DYN::m, q = MEAS::q;
   using LS = LaneS<n>;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -431,6 +507,40 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
     // loaded before its first update, so a step costs ceil(nz / RCH) memory round
     // trips instead of nz (clamped rows read valid memory and are skipped)
     constexpr int RCH = 8;
+    unsigned keep = 0xffffffffu;            // GATE: bit i clear = row i screened out
+    double nis = 0.0, lprod = 1.0;          // GATE: sum e_i^2 / s_i and prod s_i over the kept rows
+    int lexp = 0, cnt = 0;
+    if constexpr (GATE) {
+      if (a.gate < INFINITY) {
+        for (int i0 = 0; i0 < rows; i0 += RCH) {  // screening pass at (mu-, S-), chunked as below
+          double zr[RCH], pr[RCH][q > 0 ? q : 1], rr[RCH];
+#pragma unroll
+          for (int u = 0; u < RCH; ++u) {
+            const int ic = min(i0 + u, rows - 1);
+            zr[u] = zk[ic * a.es];
+#pragma unroll
+            for (int c = 0; c < q; ++c) pr[u][c] = pk[(ic * q + c) * a.es];
+            rr[u] = Rk[ic * a.nmeas_rows_max + ic];
+          }
+#pragma unroll
+          for (int u = 0; u < RCH; ++u) {
+            if (i0 + u >= rows) break;
+            double h, H[n];
+            MEAS::template row<n>(mp, pr[u], i0 + u, nz, h, H);
+            const double e = zr[u] - h;
+            double sv = rr[u];  // H_i S- H_i^T + R_ii
+#pragma unroll
+            for (int r = 0; r < n; ++r) {
+              double acc = 0.0;
+#pragma unroll
+              for (int c = 0; c < n; ++c) acc += S[LS::at(r, c)] * H[c];
+              sv += H[r] * acc;
+            }
+            if (sv > 0.0 && e * e / sv > a.gate) keep &= ~(1u << (i0 + u));
+          }
+        }
+      }
+    }
     for (int i0 = 0; i0 < rows; i0 += RCH) {
       double zr[RCH], pr[RCH][q > 0 ? q : 1], rr[RCH];
 #pragma unroll
@@ -444,6 +554,9 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
 #pragma unroll
       for (int u = 0; u < RCH; ++u) {
         if (i0 + u >= rows) break;
+        if constexpr (GATE) {
+          if (!((keep >> (i0 + u)) & 1u)) continue;
+        }
         double h, H[n];
         MEAS::template row<n>(mp, pr[u], i0 + u, nz, h, H);
         double e = zr[u] - h;
@@ -463,6 +576,13 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
         if (!(sv > 0.0 && sv < INFINITY)) status = 1;
         const double inv = 1.0 / sv;
         const double ge = e * inv;
+        if constexpr (GATE) {
+          nis += e * ge;
+          int ex;  // prod s_i as (mantissa product in [2^-32, 1)) x 2^lexp: one log per step, not per row
+          lprod *= frexp(sv, &ex);
+          lexp += ex;
+          ++cnt;
+        }
 #pragma unroll
         for (int r = 0; r < n; ++r) mu[r] += v[r] * ge;
 #pragma unroll
@@ -473,6 +593,12 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
             if (!LS::sym || c >= r) S[LS::at(r, c)] -= vr * v[c];
         }
       }
+    }
+    if constexpr (GATE) {
+      const size_t at = hist_at(a, b, k, 0, 1);
+      if (a.nis) a.nis[at] = nis;
+      if (a.loglik) a.loglik[at] = cnt ? -0.5 * (nis + (log(lprod) + lexp * LOG_2) + cnt * LOG_2PI) : 0.0;
+      if (a.rej) a.rej[at] = (int)(~keep & row_bits(rows));
     }
     // histories: with the batch-innermost layout (hist_bi) consecutive lanes write
     // consecutive words -- one coalesced 512-B store per entry instead of 64 partial lines
@@ -497,11 +623,21 @@ __global__ __launch_bounds__(256, MEAS::lane_minw) void k_ekf_lane(EkfArgs a) {
 }
 
 template <class DYN, class MEAS>
-int launch(EkfArgs& a, hipStream_t st, bool r_diag) {
+int launch(const EkfGateArgs& g, hipStream_t st, bool r_diag, bool gated) {
+  const int smem = NWF * WaveSmem<DYN::n>::total * (int)sizeof(double);
+  if (gated) {
+    const EkfGateArgs& a = g;
+    if (r_diag) {
+      hipLaunchKernelGGL((k_ekf_lane<DYN, MEAS, true>), dim3((a.batch + 255) / 256), dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((k_ekf<DYN, MEAS, true>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
+    }
+    return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+  }
+  const EkfArgs& a = g;
   if (r_diag) {
     hipLaunchKernelGGL((k_ekf_lane<DYN, MEAS>), dim3((a.batch + 255) / 256), dim3(256), 0, st, a);
   } else {
-    const int smem = NWF * WaveSmem<DYN::n>::total * (int)sizeof(double);
     hipLaunchKernelGGL((k_ekf<DYN, MEAS>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
   }
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
@@ -784,22 +920,28 @@ extern "C" int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t s
   return run(a, (hipStream_t)stream);
 }
 
-extern "C" int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* mu, double* S,
-                           const double* U, int64_t u_bstride, const double* Z, int64_t z_bstride, const int32_t* nz,
-                           int64_t nz_bstride, const double* PAR, int64_t par_bstride, const double* Q,
-                           const double* R, int64_t r_bstride, int64_t r_sstride, double* mu_hist, double* S_hist,
-                           int32_t* status, void* stream) {
+extern "C" int mhe_ekf_run_args(const mhe_ekf_dims* dims, const mhe_ekf_args* args, void* stream) {
   using namespace mhe_ekf;
-  if (!dims) return MHE_ERR_NULL;
+  if (!dims || !args) return MHE_ERR_NULL;
   if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ekf_args)) return MHE_ERR_DIMS;
+  if (!(args->gate >= 0.0)) return MHE_ERR_DIMS;  // NaN or negative; 0 = no screening, +inf allowed
+  const int32_t batch = args->batch, steps = args->steps;
   if (batch < 0 || steps < 0 || dims->pmax < 1 || dims->pmax > MAXP) return MHE_ERR_DIMS;
   if (batch == 0 || steps == 0) return MHE_OK;
-  if (!mu || !S || !Q || !nz || !Z || !R || (dims->m > 0 && !U)) return MHE_ERR_NULL;
-  EkfArgs a = {};
+  if (!args->mu || !args->S || !args->Q || !args->nz || !args->Z || !args->R || (dims->m > 0 && !args->U))
+    return MHE_ERR_NULL;
+  const double* PAR = args->PAR;
+  // the instances without the screen and the statistics serve every call that asks for neither
+  const bool gated = args->gate != 0.0 || args->nis || args->loglik || args->rej;
+  EkfGateArgs a = {};
   a.batch = batch; a.steps = steps; a.nmeas_rows_max = dims->pmax; a.dt = dims->dt;
-  a.mu = mu; a.S = S; a.U = U; a.u_bstride = u_bstride; a.Z = Z; a.z_bstride = z_bstride; a.nz = nz;
-  a.nz_bstride = nz_bstride; a.PAR = PAR; a.par_bstride = par_bstride; a.Q = Q; a.R = R; a.r_bstride = r_bstride;
-  a.r_sstride = r_sstride; a.mu_hist = mu_hist; a.S_hist = S_hist; a.status = status;
+  a.mu = args->mu; a.S = args->S; a.U = args->U; a.u_bstride = args->u_bstride; a.Z = args->Z;
+  a.z_bstride = args->z_bstride; a.nz = args->nz; a.nz_bstride = args->nz_bstride; a.PAR = PAR;
+  a.par_bstride = args->par_bstride; a.Q = args->Q; a.R = args->R; a.r_bstride = args->r_bstride;
+  a.r_sstride = args->r_sstride; a.mu_hist = args->mu_hist; a.S_hist = args->S_hist; a.status = args->status;
+  a.gate = args->gate != 0.0 ? args->gate : INFINITY;
+  a.nis = args->nis; a.loglik = args->loglik; a.rej = args->rej;
   a.hist_bi = dims->hist_batch_inner != 0;
   a.es = 1;
   if (dims->in_batch_inner) {  // U (steps, m, B), Z (steps, pmax, B), nz (steps, B), PAR (steps, pmax, q, B)
@@ -815,15 +957,29 @@ extern "C" int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t step
     if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
     switch (dims->meas_model) {
       case MHE_EKF_MEAS_MULTI_PSEUDORANGE:
-        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<false>>(a, st, rd);
+        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<false>>(a, st, rd, gated);
       case MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS:
-        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<true>>(a, st, rd);
+        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<true>>(a, st, rd, gated);
     }
   } else if (dims->dyn_model == MHE_EKF_DYN_DISCRETE_VEHICLE) {
     if (dims->n != 9 || dims->m != 2) return MHE_ERR_MODEL;
     if (!(dims->dyn_par[2] != 0.0 && dims->dyn_par[5] != 0.0)) return MHE_ERR_DIMS;  // M, I_Z unset
     if (dims->meas_model == MHE_EKF_MEAS_VEHICLE_SENSORS)
-      return launch<EkfDiscreteVehicle, EkfVehicleSensors>(a, st, rd);
+      return launch<EkfDiscreteVehicle, EkfVehicleSensors>(a, st, rd, gated);
   }
   return MHE_ERR_MODEL;
+}
+
+extern "C" int mhe_ekf_run(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, double* mu, double* S,
+                           const double* U, int64_t u_bstride, const double* Z, int64_t z_bstride, const int32_t* nz,
+                           int64_t nz_bstride, const double* PAR, int64_t par_bstride, const double* Q,
+                           const double* R, int64_t r_bstride, int64_t r_sstride, double* mu_hist, double* S_hist,
+                           int32_t* status, void* stream) {
+  mhe_ekf_args g = {};  // gate 0 and no statistics output: the instances this entry always ran
+  g.struct_size = (int32_t)sizeof(mhe_ekf_args);
+  g.batch = batch; g.steps = steps; g.mu = mu; g.S = S; g.U = U; g.u_bstride = u_bstride; g.Z = Z;
+  g.z_bstride = z_bstride; g.nz = nz; g.nz_bstride = nz_bstride; g.PAR = PAR; g.par_bstride = par_bstride; g.Q = Q;
+  g.R = R; g.r_bstride = r_bstride; g.r_sstride = r_sstride; g.mu_hist = mu_hist; g.S_hist = S_hist;
+  g.status = status;
+  return mhe_ekf_run_args(dims, &g, stream);
 }

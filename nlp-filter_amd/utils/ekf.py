@@ -147,8 +147,20 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _gate_value(gate):
+    """mhe_ekf_args.gate for run_batch's `gate`: None -> 0.0 (no screening), else a float > 0
+    (np.inf allowed); anything else raises ValueError."""
+    if gate is None:
+        return 0.0
+    if isinstance(gate, (bool, np.bool_)) or not isinstance(gate, (int, float, np.integer, np.floating)) \
+            or not float(gate) > 0.0:
+        raise ValueError(f"gate must be None or a float > 0 (np.inf allowed), not {gate!r}")
+    return float(gate)
+
+
 def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=None, stream=None,
-              keep_history=True, method="auto", inputs="batch_outer", dyn_params=None):
+              keep_history=True, method="auto", inputs="batch_outer", dyn_params=None, gate=None,
+              innovations=False):
     """Run B independent filters for T steps in one launch.
 
     mu0 (B,n), S0 (B,n,n), U (B,T,m), Z (B,T,pmax), nz (B,T) valid rows per step
@@ -168,8 +180,22 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     inputs="batch_inner": U, Z, nz, sat_pos are given batch-innermost instead,
     (T,m,B), (T,pmax,B), (T,B), (T,pmax,3,B) -- the device reads then coalesce.
 
+    gate: None, or a threshold > 0 on the normalised innovation of each row,
+    d2_i = (z_i - h_i(mu-))^2 / (H_i S- H_i^T + R_ii), evaluated at the prediction: a row
+    with d2_i > gate is screened out and the correction is the usual one on the rows that
+    remain (none: the step is predict-only).  The screen is the same for both methods.
+    10.83 is the 0.999 quantile of chi-square with one degree of freedom; np.inf screens
+    nothing.
+    innovations=True appends (nis (B,T), loglik (B,T), rejected (B,T) int32) to the
+    returned tuple: over the accepted rows a of a step, nis = e_a^T P_a^-1 e_a and
+    loglik = -(nis + log det P_a + |a| log 2 pi) / 2 (both 0 when no row was applied);
+    bit i of rejected is set iff row i was screened out.  Like the histories they are
+    views of batch-innermost storage.  Without either keyword the call and its result
+    are what they were (mhe_ekf_run's instances; otherwise mhe_ekf_run_args').
+
     stream: a torch stream to order the work on (default: the current one); outputs
     belong to it (mhe.streams)."""
+    gate = _gate_value(gate)
     import torch
 
     from mhe.streams import launch_stream
@@ -182,11 +208,11 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with launch_stream(stream, dev) as (s, cur):
         return _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history,
-                          method, inputs, dp)
+                          method, inputs, dp, gate, bool(innovations))
 
 
 def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history, method,
-               inputs, dp):
+               inputs, dp, gate=0.0, innovations=False):
     """run_batch on torch stream s (staging and allocation ordered on s)."""
     import torch
 
@@ -240,14 +266,28 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     for i in range(8):
         dims.dyn_par[i] = float(dp[i])
     lib = _lib.load()
-    rc = lib.mhe_ekf_run(ctypes.byref(dims), B, T, _ptr(mu), _ptr(S), _ptr(Ut), T * m, _ptr(Zt), T * pmax,
-                         _ptr(nzt), T, _ptr(Pt), T * pmax * q, _ptr(Qt), _ptr(Rt), r_b, r_s, _ptr(mh_st),
-                         _ptr(Sh_st), _ptr(st), ctypes.c_void_p(s.cuda_stream))
-    _lib.check(rc, "mhe_ekf_run")
-    keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st)
+    if gate == 0.0 and not innovations:
+        rc = lib.mhe_ekf_run(ctypes.byref(dims), B, T, _ptr(mu), _ptr(S), _ptr(Ut), T * m, _ptr(Zt), T * pmax,
+                             _ptr(nzt), T, _ptr(Pt), T * pmax * q, _ptr(Qt), _ptr(Rt), r_b, r_s, _ptr(mh_st),
+                             _ptr(Sh_st), _ptr(st), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ekf_run")
+        stats = ()
+    else:
+        # per-step statistics: batch-innermost (T, B) storage as the histories (hist_batch_inner)
+        stats = tuple(torch.empty((T, B), dtype=dt_, device=dev)
+                      for dt_ in (torch.float64, torch.float64, torch.int32)) if innovations else ()
+        nis, ll, rej = stats if innovations else (None, None, None)
+        args = _lib.MheEkfArgs(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
+                               Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
+                               PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
+                               r_bstride=r_b, r_sstride=r_s, mu_hist=_ptr(mh_st), S_hist=_ptr(Sh_st),
+                               status=st.data_ptr(), gate=gate, nis=_ptr(nis), loglik=_ptr(ll), rej=_ptr(rej))
+        rc = lib.mhe_ekf_run_args(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ekf_run_args")
+    keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st, *stats)
     mh = mh_st.permute(2, 0, 1) if keep_history else None
     Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
-    return mh, Sh, mu, S, st
+    return (mh, Sh, mu, S, st) + tuple(t.permute(1, 0) for t in stats)
 
 
 def _hist_storage(t, w):
@@ -270,7 +310,8 @@ def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_par
     go to the kernel without a copy; other layouts are copied to contiguous batch-outermost);
     U (B,T,m) -- or (T,m,B) with inputs="batch_inner" -- and Q (n,n), dt, dyn_params: as
     given to run_batch.  mu0 (B,n), S0 (B,n,n): optionally the prior the filter started
-    from; the smoothed prior is then returned too.
+    from; the smoothed prior is then returned too.  Measurements do not enter the backward
+    pass, so the history of a gated run (run_batch's ``gate``) smooths as any other.
     Returns (mu_s (B,T,n), S_s (B,T,n,n), status (B)) and, with a prior, also
     (mu0_s (B,n), S0_s (B,n,n)).  status 1: a predicted covariance had no Cholesky factor or
     the history held a non-finite value; that filter is NaN from the failing step down.
@@ -338,8 +379,14 @@ class EKF(object):
         self.measurement = meas_func
         models(dyn_func, meas_func)  # fail at construction for unregistered plug-ins
 
-    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None):
-        """One predict (+ correct when z is given) step, utils/ekf.py:20-38."""
+    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None, gate=None):
+        """One predict (+ correct when z is given) step, utils/ekf.py:20-38.
+
+        gate (run_batch's; np.inf: statistics only): rows of z whose normalised innovation
+        exceeds it are left out of the correction, and the object then holds ``nis``,
+        ``loglik`` (floats) and ``rejected`` (bool, one per row of z) of this update.
+        Without a gate nothing changes."""
+        gv = _gate_value(gate)
         meas = meas_func if meas_func is not None else self.measurement
         (_, n, m), (_, extra, q) = models(self.dynamics, meas)
         dt = float((dyn_func_params or {})["dt"])
@@ -361,10 +408,16 @@ class EKF(object):
             P = np.zeros((1, 1, pmax, q))
             P[0, 0, :sp.shape[0]] = sp
             Rm = np.asarray(R, dtype=np.float64).reshape(1, pmax, pmax)
-        _, _, mu, S, st = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
-                                    np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
-                                    dyn_params=dyn_func_params)
+        kw = {} if gate is None else dict(gate=gv, innovations=True)
+        out = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
+                        np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
+                        dyn_params=dyn_func_params, **kw)
+        mu, S, st = out[2:5]
         if int(st[0].item()) != 0:
             raise np.linalg.LinAlgError("innovation covariance is not positive definite")
+        if gate is not None:
+            self.nis, self.loglik = float(out[5][0, 0].item()), float(out[6][0, 0].item())
+            word = int(out[7][0, 0].item()) & 0xFFFFFFFF
+            self.rejected = np.array([bool((word >> i) & 1) for i in range(nz)], dtype=bool)
         self.mu = mu[0].cpu().numpy()
         self.S = S[0].cpu().numpy()

@@ -917,7 +917,9 @@ __device__ __forceinline__ double prior_cost(const GnArgs& a, const double* Pw, 
 // PW: the instance reads the per-solve prior weight a.Pw (prior_weight); false: the constants' only
 // SKIP: a wave whose 16 nodes are all padding (j0 + 16 wave >= P) goes straight to the
 // trailing zero fill -- see node_meas_phase
-template <class DYN, bool PW = true, bool SKIP = false>
+// OZ: the zero of the trailing fill is opaque (as a constant it is hoisted out of the Gauss-Newton
+// loop and, in the instances that run first_panel, spilled across it)
+template <class DYN, bool PW = true, bool SKIP = false, bool OZ = false>
 __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm, int b) {
   constexpr int n = DYN::n;
   const __amdgpu_buffer_rsrc_t rs = cbuf_rsrc(a.cbuf, CL.total);
@@ -994,7 +996,9 @@ __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout&
 #pragma unroll
     for (int c = 0; c < n; ++c) BV[j * n + c] = -gv[c];
   }
-  for (int t = a.d + tid; t < dp; t += NTHREADS) BV[t] = 0.0;
+  double zero = 0.0;
+  if constexpr (OZ) asm volatile("" : "+v"(zero));
+  for (int t = a.d + tid; t < dp; t += NTHREADS) BV[t] = zero;
   return cost;
 }
 
@@ -1106,7 +1110,9 @@ __device__ __forceinline__ void build_slots_n2(const GnArgs& a, const ConstLayou
 // the free unknowns, a diagonally scaled gradient step on the active ones.
 // PhiL: the measurement basis rows (a.M x a.P) staged in LDS by the caller (k_gn_general's
 // epoch rows), or nullptr = the constants' Phi
-template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false, bool PW = true>
+// SKIP0: diagonal tile 0 is not built here (the first-panel wave of k_gn's CHAIN instances
+// has built and factored it already: first_panel)
+template <class DYN, class MEAS, int SLOTS, bool HUBER = false, bool BOUNDED = false, bool PW = true, bool SKIP0 = false>
 __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
                                             d4 (&acc)[SLOTS], int wave, int lane, int stab,
                                             const double* PhiL = nullptr) {
@@ -1211,6 +1217,8 @@ __device__ __forceinline__ void build_tiles(const GnArgs& a, const ConstLayout& 
   if constexpr (PW)
     if (a.Pw) Pwb = prior_weight(a, CL, blockIdx.x);
   for (int J = wave; J < a.NT; J += NW) {
+    if constexpr (SKIP0)
+      if (J == 0) continue;
     const int ti = tile_index(J, J, a.NT);
     const size_t off = (size_t)ti * 256 + lane;
     const int col = 16 * J + (lane & 15);
@@ -1424,6 +1432,55 @@ __device__ __forceinline__ bool panel(double* DTk, const double* UN, int lane) {
   return bad != 0;
 }
 
+// The first panel of an iteration, off the factorization's chain (the CHAIN instances of
+// k_gn): diagonal tile 0 depends on Es / FtE of the nodes 0..7 and on constants only, all
+// complete at the barrier after node_meas_phase, and panel() works on LDS, so ONE wave builds
+// the tile -- the element expression of build_tiles' diagonal loop, per-solve prior weight
+// included -- and factors it while the others run the gradient phase: the wave the mat-vec
+// phases skip, where there is one (k_gn).  build_tiles<.., SKIP0> leaves the tile alone and
+// factor_forward<.., K0> starts at k = 0; the barrier after build_tiles publishes L_00^-T.
+// A bad pivot raises the NOT_SPD flag that factor_forward reads after its last barrier.
+// The tile build is a copy of build_tiles' loop body for J = 0, to be kept in step with it by
+// hand (tests/test_gpu_gn_seams.py compares the two against the small-batch instance, which
+// builds tile 0 in build_tiles).  A helper shared by both was not tried: it would recompile
+// build_tiles in every instance of the library, which sit on the register-allocation edge.
+template <class DYN, class MEAS, bool PW>
+__device__ __forceinline__ void first_panel(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm,
+                                            int lane) {
+  constexpr int n = DYN::n;
+  static_assert(n == 2 && MEAS::LINEAR, "the CHAIN instances: compact D blocks, no G term");
+  asm volatile("" : "+v"(lane));
+  const double* Cc = (const double*)(a.cbuf + CL.Cc);
+  const double* Phi = (const double*)(a.cbuf + CL.Phi);
+  const double* Es = sm + SL.Es;
+  const double* FtE = sm + SL.FtE;
+  const double* G = sm + SL.G;
+  double* DT = sm + SL.DT;
+  const double* Pwb = nullptr;
+  const double* Pwc = (const double*)(a.cbuf + CL.Pw);
+  if constexpr (PW)
+    if (a.Pw) Pwb = prior_weight(a, CL, blockIdx.x);
+  const int col = lane & 15;
+  double dav[4], dbv[4];
+  spread_dblock(((const double*)(a.cbuf + CL.DAc))[lane], dav);  // tile_index(0, 0, NT) = 0
+  spread_dblock(((const double*)(a.cbuf + CL.DBc))[lane], dbv);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int tr = (lane >> 4) + 4 * r;
+    double v = h_element<DYN, MEAS>(a, Phi, Es, FtE, G, Cc[lane + 64 * r], dav[r], dbv[r], tr, col);
+    if constexpr (PW) {
+      if (Pwb && tr < n && col < n) {
+        const int e = tr * n + col;
+        v += Pwb[e] - Pwc[e];
+      }
+    }
+    DT[tr * 16 + col] = v;
+  }
+  wave_lds_sync();
+  const bool bad = panel(DT, sm + SL.UN, lane);
+  if (bad && lane == 0) *(int*)(sm + SL.RED + 4 * NW) = 1;
+}
+
 // y = L^-1 b for one block (L^-T stored with row stride LIS), by a whole wave:
 // lane (c, g = l >> 4) sums the terms s = 4g..4g+3 of row c of L^-1, i.e. column
 // c of L^-T, rows4_sum completes the dot.  Lanes 0..15 write y[c].
@@ -1451,7 +1508,7 @@ __device__ __forceinline__ void block_fwd(const double* LT, const double* b, dou
 //     (and on in steps of NW-1): none is left for the panel wave after its panel (in LDS any
 //     wave can update any block, one wave per block and step).  Not in the instance that reads
 //     a per-solve prior weight (PW), where it costs two more SGPR spills.
-template <int SLOTS, bool CHAIN = false, bool DOFF = false>
+template <int SLOTS, bool CHAIN = false, bool DOFF = false, bool K0 = false>
 __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout& SL, double* sm,
                                                d4 (&acc)[SLOTS], int wave, int lane, int stab, DIAG_FDECL) {
   double* BV = sm + SL.BV;
@@ -1461,7 +1518,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
   int* flag = (int*)(sm + SL.RED + 4 * NW);
   const int NT = a.NT;
   bool bad = false;
-  // k = -1 is the prologue: panel(0) only
+  // k = -1 is the prologue: panel(0) only.  K0: the caller has run it (first_panel)
 #pragma unroll 1
   for (int k = -1; k + 1 < NT; ++k) {
     // opaque per-step copies: keep LICM from hoisting decoded slots and lane
@@ -1486,7 +1543,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
     const unsigned mT = (1u << sU) - (1u << sT), mU = (1u << nS) - (1u << sU);
     if (k >= 0 && wave_o == (k + 2) % NW)  // forward solve, one block behind the factorization
       block_fwd(DT + k * DTS, BV + 16 * k, YV + 16 * k, lane_o);
-    if (k >= 0) {
+    if (k >= 0 && (!CHAIN || mT != 0)) {  // CHAIN: not the operand loads and bit tests of an empty range
       const double* LT = DT + k * DTS;
       double la[4];
 #pragma unroll
@@ -1505,7 +1562,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
       }
     }
     DIAG_MARK(8);
-    __syncthreads();
+    if (!K0 || k >= 0) __syncthreads();
     DIAG_MARK(9);
     // ---- U(k)
     const int pw = CHAIN ? 0 : (k + 1) % NW;  // panel wave of this step
@@ -1528,7 +1585,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
         for (int r = 0; r < 4; ++r) DTn[r * 64 + lane_o] = t[r];
         wave_lds_sync();
       }
-      if (!KO(3)) bad |= panel(DTn, sm + SL.UN, lane_o);
+      if (!KO(3) && !(K0 && k < 0)) bad |= panel(DTn, sm + SL.UN, lane_o);
       __builtin_amdgcn_s_setprio(0);
     } else if (k >= 0 && !KO(4)) {
       // b_b -= U_kb^T y_k for b >= k + 1: one output per lane of the other waves
@@ -1547,7 +1604,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
     }
     DIAG_MARK(12);
     // off-diagonal trailing update over the slot suffix [sU, nS)
-    if (k >= 0 && !KO(1)) {
+    if (k >= 0 && !KO(1) && (!CHAIN || mU != 0)) {
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
         if ((mU >> s) & 1u) {
@@ -1591,7 +1648,7 @@ __device__ __forceinline__ bool factor_forward(const GnArgs& a, const SmemLayout
       for (int r = 0; r < 4; ++r) DTj[r * 64 + lane_o] = t[r];
     }
     DIAG_MARK(10);
-    __syncthreads();  // PB is single-buffered; DT[k+1] / y_{k+1} complete
+    if (!K0 || k >= 0) __syncthreads();  // PB is single-buffered; DT[k+1] / y_{k+1} complete
     DIAG_MARK(11);
   }
   if (bad && lane == 0) flag[0] = 1;  // flag was zeroed at kernel start
@@ -1959,7 +2016,9 @@ __device__ __forceinline__ void block_back(const double* LT, double* yv, int lan
 // One workgroup barrier per block.
 // YLAST: the caller has formed y_{NT-1} already (k_gn_general: the bordered step corrects
 // all of y between the factorization and this solve)
-template <int SLOTS, bool YLAST = false>
+// EMPTY (the CHAIN instances of k_gn): a wave with no tile in block column bb skips the slot
+// loop's bit tests (wave 0, the panel wave, holds tiles in block rows 0..4 only)
+template <int SLOTS, bool YLAST = false, bool EMPTY = false>
 __device__ __forceinline__ void backward(const GnArgs& a, const SmemLayout& SL, double* sm,
                                          d4 (&acc)[SLOTS], int wave, int lane, int stab) {
   const double* DT = sm + SL.DT;
@@ -1985,6 +2044,7 @@ __device__ __forceinline__ void backward(const GnArgs& a, const SmemLayout& SL, 
     // column-major index, and its owner's delta_{bb-1} is the critical chain
 #pragma unroll
     for (int s = SLOTS - 1; s >= 0; --s) {
+      if (EMPTY && rm == 0) break;  // wave-uniform
       if (!((rm >> s) & 1u)) continue;
       const int IJ = slot_ij(stab_o, s);
       const int J = IJ >> 16;
@@ -2317,7 +2377,13 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     DIAG_MARK(6);
     __syncthreads();
     DIAG_MARK(0);
-    c1 += grad_phase<DYN, PW, TRIM>(FA, FCL, FSL, sm, opaque_s(b));
+    if constexpr (CHAIN) {
+      // the first panel, by the wave that has nothing to do in the mat-vec phases: wave 7 when
+      // its rows are all padding (P, M <= 112: the SKIP test of the phases), else wave 0
+      const int pp = opaque_s(a.P), mm = opaque_s(a.M), pm = pp > mm ? pp : mm;
+      if (wave == (16 * (NW - 1) >= pm ? NW - 1 : 0)) first_panel<DYN, MEAS, PW>(FA, FCL, FSL, sm, lane);
+    }
+    c1 += grad_phase<DYN, PW, TRIM, CHAIN>(FA, FCL, FSL, sm, opaque_s(b));
     if constexpr (!TRIM) {
       // park this wave's part of the cost in LDS (a live register across the
       // factorization would spill): read back if the loop exits at this iterate
@@ -2370,7 +2436,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     }
     if constexpr (!TRIM)
       if (it >= a.max_iter) break;
-    build_tiles<DYN, MEAS, SLOTS, HUBER, false, PW>(FA, FCL, FSL, sm, acc, wave, lane, stab);
+    build_tiles<DYN, MEAS, SLOTS, HUBER, false, PW, CHAIN>(FA, FCL, FSL, sm, acc, wave, lane, stab);
     DIAG_MARK(15);
     __syncthreads();
     DIAG_MARK(2);
@@ -2378,7 +2444,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     if constexpr (SB)
       ok = factor_forward_sb<SLOTS>(FA, FSL, sm, acc, wave, lane, stab, sbm, DIAG_FARGS);
     else
-      ok = factor_forward<SLOTS, CHAIN, CHAIN && !PW>(FA, FSL, sm, acc, wave, lane, stab, DIAG_FARGS);
+      ok = factor_forward<SLOTS, CHAIN, CHAIN && !PW, CHAIN>(FA, FSL, sm, acc, wave, lane, stab, DIAG_FARGS);
     DIAG_MARK(3);
     if (!ok) {
       status = MHE_STATUS_NOT_SPD;
@@ -2387,7 +2453,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void k_gn(GnArgs a) {
     if constexpr (SB)
       backward_sb<SLOTS>(FA, FSL, sm, acc, wave, lane, stab);
     else
-      backward<SLOTS>(FA, FSL, sm, acc, wave, lane, stab);
+      backward<SLOTS, false, CHAIN>(FA, FSL, sm, acc, wave, lane, stab);
     DIAG_MARK(4);
     // X += delta (bounded problems run k_gn_bounded).  A non-finite delta is flagged
     // as an infinite step (NONFINITE, X untouched).

@@ -710,6 +710,62 @@ typedef struct mhe_ekf_args {
 int mhe_ekf_run_args(const mhe_ekf_dims* dims, const mhe_ekf_args* args, void* stream);
 
 /*
+ * Batched unscented Kalman filter (added within v11; no existing struct or function changed).
+ * The additive-noise filter with the scaled unscented transform over the same plug-ins, by
+ * their VALUES only: no Jacobian enters, so the bias row of
+ * MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS (h = x[3]) acts, and MHE_EKF_DYN_DISCRETE_VEHICLE is
+ * its Euler step.  One wavefront per filter.  With lambda = alpha^2 (n + kappa) - n,
+ * c = sqrt(n + lambda), wm_0 = lambda / (n + lambda), wc_0 = wm_0 + 1 - alpha^2 + beta and
+ * wm_j = wc_j = 1 / (2 (n + lambda)), the 2n+1 sigma points of (mu, S = L L^T) are mu and
+ * mu +- c L[:, j].  Per step:
+ *   predict  Y_j = f(X_j, u),  mu- = sum wm_j Y_j,  S- = sum wc_j (Y_j - mu-)(Y_j - mu-)^T + Q
+ *   correct  (0 < nz <= pmax) with sigma points redrawn from (mu-, S-):  Zs_j = h(X_j) - z,
+ *            e = -sum wm_j Zs_j,  Dz_j = Zs_j + e,  Pzz = sum wc_j Dz_j Dz_j^T + R,
+ *            Pxz = sum wc_j (X_j - mu-) Dz_j^T;  with Pzz = L L^T, Y = L^-1 Pxz^T, w = L^-1 e:
+ *            mu = mu- + Y^T w,  S = S- - Y^T Y
+ * Every sum runs over j in increasing order, so a filter's result does not depend on the batch
+ * or on its place in it.  Only the upper triangles of Q and R are read; S_hist and S are bitwise
+ * symmetric.
+ * dims, the input layouts and strides and the history layout are mhe_ekf_run's (r_diag is
+ * ignored); the fields of mhe_ukf_args up to status are mhe_ekf_args', then
+ *   alpha, beta, kappa   1, 0, 0 gives lambda = 0: 2n equally weighted points, no negative
+ *           weight.  alpha not finite or <= 0, beta or kappa not finite, n + kappa <= 0:
+ *           MHE_ERR_DIMS
+ *   nis, loglik   optional per-step outputs laid out as mhe_ekf_args': nis = w^T w,
+ *           loglik = -(nis + 2 sum log L_ii + nz log 2 pi) / 2; 0 on a step without a correction.
+ * status (B, optional): 0 ok; 1 a Cholesky pivot of S, S- or Pzz was not positive and finite:
+ * that filter's history entries (nis and loglik included) from that step on and its final
+ * mu / S are NaN, every other filter is untouched; 2 nz > pmax at some step (that step is
+ * predict-only).  Refusals and return codes are mhe_ekf_run_args' (batch == 0 or steps == 0:
+ * MHE_OK, nothing is read).
+ */
+typedef struct mhe_ukf_args {
+  int32_t struct_size; /* = sizeof(mhe_ukf_args) */
+  int32_t batch, steps;
+  double* mu;
+  double* S;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const double* Q;
+  const double* R;
+  int64_t r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int32_t* status;
+  double alpha, beta, kappa;
+  double* nis;
+  double* loglik;
+} mhe_ukf_args;
+
+int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream);
+
+/*
  * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
  * (added to ABI v11; no existing struct or function changed).  One filter per lane;
  * a filter's result does not depend on the batch or on its place in it.

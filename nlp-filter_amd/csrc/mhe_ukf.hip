@@ -1,0 +1,387 @@
+// libmhe: batched unscented Kalman filter for MI355X (gfx950).
+//
+// The additive-noise UKF with the scaled unscented transform (include/mhe.h states the
+// recursion) over the plug-ins of the batched EKF, by their values only (DYN::f, MEAS::h of
+// mhe_ekf_models.h): no Jacobian enters.  ONE WAVEFRONT PER FILTER runs all `steps` updates of
+// its instance, four instances per workgroup, per-wave LDS scratch, wave barriers and
+// wavefront fences between phases, no workgroup barrier -- the layout of k_ekf.
+//   * Cholesky of S / S- (n <= 9): row per lane in registers, right-looking, pivots and L_jc
+//     broadcast by v_readlane; true sqrt and division.
+//   * sigma points: one per lane (2n+1 <= 19 lanes) for the propagation; the nz x (2n+1)
+//     measurement evaluations are strided over the 64 lanes.
+//   * S-, Pzz (upper triangles, then mirrored / read as (min, max)) and Pxz: one entry per
+//     lane-iteration, each summed over j = 0 .. 2n in that order.
+//   * the correction is k_ekf's augmented right-looking sweep, here over [Pzz | Pxz^T | e]:
+//     Y = L^-1 Pxz^T, w = L^-1 e, mu = mu- + Y^T w, S = S- - Y^T Y.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "mhe.h"
+#include "mhe_ekf_models.h"
+
+namespace mhe_ukf {
+
+using mhe_ekf::readlane_d;
+
+constexpr int NWF = 4;     // filters (waves) per workgroup
+constexpr int MAXP = 32;   // measurement rows per step (nz <= pmax <= MAXP; mhe_ukf_run checks pmax)
+constexpr int TRI = MAXP * (MAXP + 1) / 2;
+constexpr double LOG_2PI = 1.8378770664093454836;
+
+struct UkfArgs {
+  int batch, steps, nmeas_rows_max;
+  double dt;
+  double dp[8];  // static dynamics parameters (mhe_ekf_dims.dyn_par)
+  double c, wm0, wc0, wi;  // sqrt(n + lambda) and the weights of point 0 (mean, covariance) and of the others
+  double* mu;
+  double* S;
+  const double* U;
+  long long u_bstride;
+  const double* Z;
+  long long z_bstride;
+  const int* nz;
+  long long nz_bstride;
+  const double* PAR;
+  long long par_bstride;
+  const double* Q;
+  const double* R;
+  long long r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int hist_bi;   // 1: histories batch-innermost, as k_ekf's
+  long long es;  // element stride of U / Z / nz / PAR, as k_ekf's
+  int* status;
+  double* nis;   // per-step statistics, optional: (steps, B) with hist_bi, else (B, steps)
+  double* loglik;
+};
+
+// element (b, k, e) of a per-step history with `w` entries per step
+__device__ __forceinline__ size_t hist_at(const UkfArgs& a, int b, int k, int e, int w) {
+  return a.hist_bi ? ((size_t)k * w + e) * a.batch + b : ((size_t)b * a.steps + k) * w + e;
+}
+
+// entry t (r <= c) of the upper triangle of an N x N matrix, t < N (N + 1) / 2: row a
+// (N - a entries) and the row that completes it to N | 1 entries share one line of a folded
+// rectangle, so consecutive t are consecutive entries and no lane draws a skipped one
+__device__ __forceinline__ void tri_rc(int t, int N, int& r, int& c) {
+  const int w = N | 1;
+  const int a = t / w, b = t - a * w;
+  if (b < N - a) {
+    r = a;
+    c = a + b;
+  } else {
+    r = N - a - ((N & 1) ^ 1);
+    c = r + (b - (N - a));
+  }
+}
+
+// packed upper triangle of a MAXP x MAXP matrix (row stride fixed, whatever nz is)
+__device__ __forceinline__ int tri_at(int r, int c) { return r * MAXP - r * (r - 1) / 2 + (c - r); }
+
+// per-wave LDS scratch (doubles).  A holds S, then its factor L, then L of S-; XS the
+// propagated points Y_j, then the points redrawn from (mu-, S-); ZS the measurement values
+// Zs_j and then Dz_j, point-major with MAXP rows each; PZ the packed upper triangle of Pzz;
+// T1 row i of Pxz^T and then of Y; E the vector w.
+template <int n>
+struct WaveSmem {
+  static constexpr int NS = 2 * n + 1;
+  static constexpr int MU = 0, MP = MU + n, A = MP + n, SP = A + n * n, XS = SP + n * n, ZS = XS + NS * n,
+                       PZ = ZS + NS * MAXP, T1 = PZ + TRI, E = T1 + MAXP * n, total = E + MAXP;
+};
+
+#define UKF_PHASE()                  \
+  __builtin_amdgcn_wave_barrier();   \
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
+
+// M (n x n in LDS, row major) = L L^T in place: lane i < n holds row i in registers; column c's
+// pivot and every L_jc come by readlane.  The strict upper triangle of L is written as zeros.
+// Returns (wave-uniform) whether every pivot was positive and finite.
+template <int n>
+__device__ __forceinline__ bool chol_inplace(double* M, int lane) {
+  double s[n];
+#pragma unroll
+  for (int c = 0; c < n; ++c) s[c] = lane < n ? M[lane * n + c] : 0.0;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < n; ++c) {
+    const double piv = readlane_d(s[c], c);
+    ok &= (piv > 0.0 && piv < INFINITY);
+    const double d = sqrt(piv);
+    const double l = lane == c ? d : s[c] / d;  // L_ic
+#pragma unroll
+    for (int j = c + 1; j < n; ++j) s[j] -= l * readlane_d(l, j);
+    s[c] = lane >= c ? l : 0.0;
+  }
+  if (lane < n) {
+#pragma unroll
+    for (int c = 0; c < n; ++c) M[lane * n + c] = s[c];
+  }
+  return ok;
+}
+
+// sigma point j of (mean, L): X_0 = mean, X_j = mean + c L[:, j-1], X_{n+j} = mean - c L[:, j-1]
+template <int n>
+__device__ __forceinline__ void sigma_point(const double* mean, const double* L, double c, int j, double* x) {
+  const int col = j == 0 ? 0 : (j <= n ? j - 1 : j - n - 1);
+  const double sc = j == 0 ? 0.0 : (j <= n ? c : -c);
+#pragma unroll
+  for (int r = 0; r < n; ++r) x[r] = j == 0 ? mean[r] : mean[r] + sc * L[r * n + col];
+}
+
+template <class DYN, class MEAS>
+__global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
+  constexpr int n = DYN::n, m = DYN::m, q = MEAS::q;
+  using WS = WaveSmem<n>;
+  constexpr int NS = WS::NS;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * NWF + wave;
+  if (b >= a.batch) return;  // whole wave exits; no workgroup barrier is used below
+  double* sw = smem + wave * WS::total;
+  double* mu = sw + WS::MU;
+  double* MP = sw + WS::MP;
+  double* A = sw + WS::A;
+  double* SP = sw + WS::SP;
+  double* XS = sw + WS::XS;
+  double* ZS = sw + WS::ZS;
+  double* PZ = sw + WS::PZ;
+  double* T1 = sw + WS::T1;
+  double* E = sw + WS::E;
+  for (int t = lane; t < n; t += 64) mu[t] = a.mu[(size_t)b * n + t];
+  for (int t = lane; t < n * n; t += 64) A[t] = a.S[(size_t)b * n * n + t];
+  int status = 0;
+  bool dead = false;  // a pivot failed: this filter's outputs are NaN from that step on
+  UKF_PHASE();
+  for (int k = 0; k < a.steps; ++k) {
+    // ---- predict: sigma points of (mu, S), one per lane, through the dynamics
+    dead |= !chol_inplace<n>(A, lane);
+    UKF_PHASE();
+    if (lane < NS) {
+      double x[n], u[m > 0 ? m : 1], xp[n];
+      sigma_point<n>(mu, A, a.c, lane, x);
+      for (int c = 0; c < m; ++c) u[c] = a.U[(long long)b * a.u_bstride + ((long long)k * m + c) * a.es];
+      DYN::f(x, u, a.dt, a.dp, xp);
+      for (int c = 0; c < n; ++c) XS[lane * n + c] = xp[c];
+    }
+    UKF_PHASE();
+    if (lane < n) {  // mu- = sum wm_j Y_j
+      double acc = a.wm0 * XS[lane];
+      for (int j = 1; j < NS; ++j) acc += a.wi * XS[j * n + lane];
+      MP[lane] = acc;
+    }
+    UKF_PHASE();
+    for (int t = lane; t < n * (n + 1) / 2; t += 64) {  // S- = sum wc_j (Y_j - mu-)(Y_j - mu-)^T + Q
+      int r, c;
+      tri_rc(t, n, r, c);
+      const double mr = MP[r], mc = MP[c];
+      double acc = a.wc0 * ((XS[r] - mr) * (XS[c] - mc));
+      for (int j = 1; j < NS; ++j) acc += a.wi * ((XS[j * n + r] - mr) * (XS[j * n + c] - mc));
+      acc += a.Q[r * n + c];
+      SP[r * n + c] = acc;
+      SP[c * n + r] = acc;
+    }
+    UKF_PHASE();
+    const int nz = a.nz[(long long)b * a.nz_bstride + (long long)k * a.es];
+    double nis = 0.0, loglik = 0.0;
+    // Z / PAR / R hold pmax (<= MAXP) rows per step: a step that claims more is refused
+    if (nz > 0 && nz <= a.nmeas_rows_max) {
+      // ---- sigma points redrawn from (mu-, S-)
+      for (int t = lane; t < n * n; t += 64) A[t] = SP[t];
+      UKF_PHASE();
+      dead |= !chol_inplace<n>(A, lane);
+      UKF_PHASE();
+      if (lane < NS) {
+        double x[n];
+        sigma_point<n>(MP, A, a.c, lane, x);
+        for (int c = 0; c < n; ++c) XS[lane * n + c] = x[c];
+      }
+      UKF_PHASE();
+      // ---- Zs_j = h(X_j) - z: centred on the measurement, nz x (2n+1) evaluations
+      const long long rk0 = (long long)k * a.nmeas_rows_max;  // first row of the step within the instance
+      for (int t = lane; t < nz * NS; t += 64) {
+        const int j = t / nz, i = t - j * nz;
+        double x[n], par[q > 0 ? q : 1];
+        for (int c = 0; c < n; ++c) x[c] = XS[j * n + c];
+        for (int c = 0; c < q; ++c) par[c] = a.PAR[(long long)b * a.par_bstride + ((rk0 + i) * q + c) * a.es];
+        ZS[j * MAXP + i] = MEAS::template h<n>(x, par, i, nz) - a.Z[(long long)b * a.z_bstride + (rk0 + i) * a.es];
+      }
+      UKF_PHASE();
+      double e = 0.0;
+      if (lane < nz) {  // e = -sum wm_j Zs_j; Dz_j = Zs_j + e in place
+        double acc = a.wm0 * ZS[lane];
+        for (int j = 1; j < NS; ++j) acc += a.wi * ZS[j * MAXP + lane];
+        e = -acc;
+        for (int j = 0; j < NS; ++j) ZS[j * MAXP + lane] += e;
+      }
+      UKF_PHASE();
+      const double* Rk = a.R + (long long)b * a.r_bstride + (long long)k * a.r_sstride;
+      for (int t = lane; t < nz * (nz + 1) / 2; t += 64) {  // Pzz = sum wc_j Dz_j Dz_j^T + R, upper triangle
+        int r, c;
+        tri_rc(t, nz, r, c);
+        double acc = a.wc0 * (ZS[r] * ZS[c]);
+        for (int j = 1; j < NS; ++j) acc += a.wi * (ZS[j * MAXP + r] * ZS[j * MAXP + c]);
+        PZ[tri_at(r, c)] = acc + Rk[r * a.nmeas_rows_max + c];
+      }
+      for (int t = lane; t < nz * n; t += 64) {  // Pxz^T = sum wc_j Dz_j (X_j - mu-)^T, row i per measurement
+        const int i = t / n, c = t % n;
+        const double mc = MP[c];
+        double acc = a.wc0 * ((XS[c] - mc) * ZS[i]);
+        for (int j = 1; j < NS; ++j) acc += a.wi * ((XS[j * n + c] - mc) * ZS[j * MAXP + i]);
+        T1[t] = acc;
+      }
+      UKF_PHASE();
+      // ---- augmented sweep: lane i holds row i of [Pzz | Pxz^T | e]
+      const int i = lane;
+      const bool row = i < nz;
+      double p[MAXP], t1[n];
+#pragma unroll
+      for (int j = 0; j < MAXP; ++j) {
+        const int ii = i < MAXP ? i : 0;
+        p[j] = (row && j < nz) ? PZ[j < ii ? tri_at(j, ii) : tri_at(ii, j)] : 0.0;
+      }
+#pragma unroll
+      for (int c = 0; c < n; ++c) t1[c] = row ? T1[i * n + c] : 0.0;
+      double idg = 0.0;
+      bool bad = false;
+#pragma unroll
+      for (int c = 0; c < MAXP; ++c) {
+        if (c < nz) {
+          const double piv = readlane_d(p[c], c);
+          bad |= !(piv > 0.0 && piv < INFINITY);
+          const double rs = 1.0 / sqrt(piv);
+          const double qv = p[c] * rs;                      // L_ic (i > c)
+          const double mm = (i > c && row) ? qv * rs : 0.0;  // A'_ic / A'_cc
+          idg = (i == c) ? rs : idg;
+#pragma unroll
+          for (int j = c + 1; j < MAXP; ++j)
+            if (j < nz) p[j] -= qv * readlane_d(qv, j);
+#pragma unroll
+          for (int cc = 0; cc < n; ++cc) t1[cc] -= mm * readlane_d(t1[cc], c);
+          e -= mm * readlane_d(e, c);
+        }
+      }
+      dead |= bad;
+      if (row) {
+#pragma unroll
+        for (int c = 0; c < n; ++c) T1[i * n + c] = t1[c] * idg;  // Y = L^-1 Pxz^T
+        E[i] = e * idg;                                          // w = L^-1 e
+      }
+      if (a.nis || a.loglik) {  // wave-uniform
+        // nis = w^T w, sum log L_ii = -sum log(1 / L_ii): the rows sit in lanes 0..31
+        double s2 = row ? (e * idg) * (e * idg) : 0.0;
+        double lg = row ? log(idg) : 0.0;
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+          s2 += __shfl_xor(s2, off);
+          lg += __shfl_xor(lg, off);
+        }
+        nis = s2;
+        loglik = -0.5 * (s2 - 2.0 * lg + nz * LOG_2PI);
+      }
+      UKF_PHASE();
+      // mu = mu- + Y^T w ; S = S- - Y^T Y (upper triangle, mirrored)
+      for (int t = lane; t < n * (n + 1) / 2; t += 64) {
+        int r, c;
+        tri_rc(t, n, r, c);
+        double acc = 0.0;
+        for (int ii = 0; ii < nz; ++ii) acc += T1[ii * n + r] * T1[ii * n + c];
+        const double v = SP[r * n + c] - acc;
+        A[r * n + c] = v;
+        A[c * n + r] = v;
+      }
+      for (int t = lane; t < n; t += 64) {
+        double acc = 0.0;
+        for (int ii = 0; ii < nz; ++ii) acc += T1[ii * n + t] * E[ii];
+        mu[t] = MP[t] + acc;
+      }
+    } else {
+      if (nz > a.nmeas_rows_max) status = 2;
+      for (int t = lane; t < n * n; t += 64) A[t] = SP[t];
+      for (int t = lane; t < n; t += 64) mu[t] = MP[t];
+    }
+    if (dead) {
+      nis = loglik = NAN;
+      for (int t = lane; t < n * n; t += 64) A[t] = NAN;
+      for (int t = lane; t < n; t += 64) mu[t] = NAN;
+    }
+    UKF_PHASE();
+    if (lane == 0) {
+      const size_t at = hist_at(a, b, k, 0, 1);
+      if (a.nis) a.nis[at] = nis;
+      if (a.loglik) a.loglik[at] = loglik;
+    }
+    if (a.mu_hist)
+      for (int t = lane; t < n; t += 64) a.mu_hist[hist_at(a, b, k, t, n)] = mu[t];
+    if (a.S_hist)
+      for (int t = lane; t < n * n; t += 64) a.S_hist[hist_at(a, b, k, t, n * n)] = A[t];
+  }
+  for (int t = lane; t < n; t += 64) a.mu[(size_t)b * n + t] = mu[t];
+  for (int t = lane; t < n * n; t += 64) a.S[(size_t)b * n * n + t] = A[t];
+  if (a.status && lane == 0) a.status[b] = dead ? 1 : status;
+}
+
+#undef UKF_PHASE
+
+template <class DYN, class MEAS>
+int launch(const UkfArgs& a, hipStream_t st) {
+  const int smem = NWF * WaveSmem<DYN::n>::total * (int)sizeof(double);
+  hipLaunchKernelGGL((k_ukf<DYN, MEAS>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
+}  // namespace mhe_ukf
+
+extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream) {
+  using namespace mhe_ukf;
+  using namespace mhe_ekf;
+  if (!dims || !args) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ukf_args)) return MHE_ERR_DIMS;
+  const double al = args->alpha, be = args->beta, ka = args->kappa;
+  if (!(al > 0.0 && al < INFINITY) || !(fabs(be) < INFINITY) || !(fabs(ka) < INFINITY)) return MHE_ERR_DIMS;
+  const double nn = (double)dims->n;
+  if (!(nn + ka > 0.0)) return MHE_ERR_DIMS;
+  const double lam = al * al * (nn + ka) - nn;  // n + lambda = alpha^2 (n + kappa) > 0
+  if (!(nn + lam > 0.0 && nn + lam < INFINITY)) return MHE_ERR_DIMS;  // alpha^2 (n + kappa) under- or overflowed
+  const int32_t batch = args->batch, steps = args->steps;
+  if (batch < 0 || steps < 0 || dims->pmax < 1 || dims->pmax > MAXP) return MHE_ERR_DIMS;
+  if (batch == 0 || steps == 0) return MHE_OK;
+  if (!args->mu || !args->S || !args->Q || !args->nz || !args->Z || !args->R || (dims->m > 0 && !args->U))
+    return MHE_ERR_NULL;
+  if (dims->q != 3) return MHE_ERR_DIMS;
+  if (!args->PAR) return MHE_ERR_NULL;
+  int (*run)(const UkfArgs&, hipStream_t) = nullptr;
+  if (dims->dyn_model == MHE_EKF_DYN_GNSS_POS_AND_BIAS) {
+    if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
+    if (dims->meas_model == MHE_EKF_MEAS_MULTI_PSEUDORANGE)
+      run = launch<EkfGnssPosAndBias, EkfMultiPseudorange<false>>;
+    else if (dims->meas_model == MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS)
+      run = launch<EkfGnssPosAndBias, EkfMultiPseudorange<true>>;
+  } else if (dims->dyn_model == MHE_EKF_DYN_DISCRETE_VEHICLE) {
+    if (dims->n != 9 || dims->m != 2) return MHE_ERR_MODEL;
+    if (!(dims->dyn_par[2] != 0.0 && dims->dyn_par[5] != 0.0)) return MHE_ERR_DIMS;  // M, I_Z unset
+    if (dims->meas_model == MHE_EKF_MEAS_VEHICLE_SENSORS) run = launch<EkfDiscreteVehicle, EkfVehicleSensors>;
+  }
+  if (!run) return MHE_ERR_MODEL;
+  UkfArgs a = {};
+  a.batch = batch; a.steps = steps; a.nmeas_rows_max = dims->pmax; a.dt = dims->dt;
+  for (int i = 0; i < 8; ++i) a.dp[i] = dims->dyn_par[i];
+  a.c = sqrt(nn + lam);
+  a.wm0 = lam / (nn + lam);
+  a.wc0 = a.wm0 + 1.0 - al * al + be;
+  a.wi = 1.0 / (2.0 * (nn + lam));
+  a.mu = args->mu; a.S = args->S; a.U = args->U; a.u_bstride = args->u_bstride; a.Z = args->Z;
+  a.z_bstride = args->z_bstride; a.nz = args->nz; a.nz_bstride = args->nz_bstride; a.PAR = args->PAR;
+  a.par_bstride = args->par_bstride; a.Q = args->Q; a.R = args->R; a.r_bstride = args->r_bstride;
+  a.r_sstride = args->r_sstride; a.mu_hist = args->mu_hist; a.S_hist = args->S_hist; a.status = args->status;
+  a.nis = args->nis; a.loglik = args->loglik;
+  a.hist_bi = dims->hist_batch_inner != 0;
+  a.es = 1;
+  if (dims->in_batch_inner) {  // U (steps, m, B), Z (steps, pmax, B), nz (steps, B), PAR (steps, pmax, q, B)
+    a.es = batch;
+    a.u_bstride = a.z_bstride = a.nz_bstride = a.par_bstride = 1;
+  }
+  return run(a, (hipStream_t)stream);
+}

@@ -58,6 +58,14 @@ class MheEkfArgs(_Sized):
                 ("nis", c_vp), ("loglik", c_vp), ("rej", c_vp)]
 
 
+class MheUkfArgs(_Sized):
+    _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu", c_vp), ("S", c_vp), ("U", c_vp),
+                ("u_bstride", c_i64), ("Z", c_vp), ("z_bstride", c_i64), ("nz", c_vp), ("nz_bstride", c_i64),
+                ("PAR", c_vp), ("par_bstride", c_i64), ("Q", c_vp), ("R", c_vp), ("r_bstride", c_i64),
+                ("r_sstride", c_i64), ("mu_hist", c_vp), ("S_hist", c_vp), ("status", c_vp), ("alpha", c_dbl),
+                ("beta", c_dbl), ("kappa", c_dbl), ("nis", c_vp), ("loglik", c_vp)]
+
+
 class MheLsDims(_Sized):
     _fields_ = [("struct_size", c_i32), ("slots", c_i32), ("max_iter", c_i32), ("warm", c_i32), ("with_vel", c_i32), ("tol", c_dbl)]
 
@@ -120,6 +128,7 @@ SIGNATURES = {
     "mhe_ekf_run": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ekf_run_args": (ctypes.c_int, [_PE, ctypes.POINTER(MheEkfArgs), c_vp]),
+    "mhe_ukf_run": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfArgs), c_vp]),
     "mhe_ekf_smooth": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

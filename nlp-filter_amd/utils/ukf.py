@@ -1,0 +1,196 @@
+"""Unscented Kalman filter on the GPU -- the Jacobian-free companion of ``utils.ekf``.
+
+``run_batch`` runs many independent filters over many steps in one launch of
+``mhe_ukf_run`` (csrc/mhe_ukf.hip, one wavefront per filter); ``UKF(dyn_func, meas_func,
+mu0, S0)`` / ``UKF.update(u, z, Q, R, ...)`` have ``utils.ekf.EKF``'s signature and
+semantics, one launch per update.  The filter is the additive-noise UKF with the scaled
+unscented transform (include/mhe.h states the recursion): sigma points are redrawn from
+the prediction before the correction, the measurement values are centred on z before
+they are averaged, and the correction is a Cholesky sweep of Pzz with no explicit inverse.
+
+Only the plug-ins' *values* enter, so neither of the EKF's reference-compatible Jacobian
+quirks does: the bias row of ``multi_pseudorange_and_bias`` (h = x[3]) acts here, and
+``discrete_vehicle_dynamics`` is its plain Euler step.  Plug-ins resolve and are verified
+exactly as for the EKF (``utils.ekf.models`` / ``verify``); there is no CPU path.
+
+Why the defaults are alpha = 1, beta = 0, kappa = 0: they give lambda = 0, that is 2n
+equally weighted points and no negative weight.  With the textbook alpha = 1e-3 the
+centre weight is about -1e6 and the weighted sums cancel at that magnitude: in float64
+the rounding floor of the gnss position rose from 1.6e-6 m to 1.6e-3 m.  alpha, beta and
+kappa remain parameters.
+
+Not formed: innovation gating, a filter-per-lane kernel, an unscented RTS pass
+(``utils.ekf.smooth_batch`` over a UKF history is the EKF-linearised smoother).
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from mhe import _lib
+
+from . import ekf as _ekf
+
+MAXP = _ekf.MAXP
+
+
+def _real(v):
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def sigma_params(alpha, beta, kappa, n):
+    """(alpha, beta, kappa) as floats, or ValueError: alpha must be finite and > 0, beta and
+    kappa finite, and n + kappa > 0 (so that n + lambda = alpha^2 (n + kappa) > 0)."""
+    for name, v in (("alpha", alpha), ("beta", beta), ("kappa", kappa)):
+        if not _real(v) or not math.isfinite(float(v)):
+            raise ValueError(f"{name} must be a finite number, not {v!r}")
+    if not float(alpha) > 0.0:
+        raise ValueError(f"alpha must be > 0, not {alpha!r}")
+    if not n + float(kappa) > 0.0:
+        raise ValueError(f"n + kappa must be > 0 (n = {n}, kappa = {kappa!r})")
+    s = float(alpha) * float(alpha) * (n + float(kappa))
+    if not (s > 0.0 and math.isfinite(s)):
+        raise ValueError(f"alpha^2 (n + kappa) = {s!r} is not a positive finite number")
+    return float(alpha), float(beta), float(kappa)
+
+
+def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=None, stream=None,
+              keep_history=True, inputs="batch_outer", dyn_params=None, alpha=1.0, beta=0.0, kappa=0.0,
+              innovations=False):
+    """Run B independent unscented filters for T steps in one launch.
+
+    Shapes, layouts (``inputs``) and ``stream`` are ``utils.ekf.run_batch``'s: mu0 (B,n),
+    S0 (B,n,n), U (B,T,m), Z (B,T,pmax), nz (B,T) valid rows per step (0 = predict only),
+    Q (n,n), R (T,pmax,pmax) or (B,T,pmax,pmax), sat_pos (B,T,pmax,3); only the upper
+    triangles of Q and R are read.
+    Returns (mu_hist (B,T,n), S_hist (B,T,n,n), mu (B,n), S (B,n,n), status (B)) on the
+    device; S_hist and S are bitwise symmetric.  status: 0 ok; 1 a Cholesky pivot of S, S-
+    or Pzz was not positive and finite -- that filter's history from that step on and its
+    final mu / S are NaN, no other filter is touched; 2 nz > pmax at some step (that step is
+    predict-only).
+    innovations=True appends (nis (B,T), loglik (B,T)): nis = e^T Pzz^-1 e and
+    loglik = -(nis + log det Pzz + nz log 2 pi) / 2, both 0 on a step without a correction.
+    alpha, beta, kappa: the scaled unscented transform's parameters (see the module
+    docstring for the defaults); a bad value raises ValueError."""
+    (did, n, m), (mid, _, q) = _ekf.models(dyn_func, meas_func)
+    alpha, beta, kappa = sigma_params(alpha, beta, kappa, n)
+    import torch
+
+    from mhe.streams import launch_stream
+
+    if dyn_params is not None and "dt" in dyn_params:
+        dt = dyn_params["dt"]
+    _ekf.verify(dyn_func, meas_func, dict(dyn_params or {}, dt=dt))
+    dp = _ekf.dyn_par(dyn_func, dyn_params)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with launch_stream(stream, dev) as (s, cur):
+        return _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history,
+                          inputs, dp, alpha, beta, kappa, bool(innovations))
+
+
+def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history, inputs, dp,
+               alpha, beta, kappa, innovations):
+    """run_batch on torch stream s (staging and allocation ordered on s)."""
+    import torch
+
+    from mhe.streams import keep_alive
+
+    def d(a, dt_=torch.float64):
+        return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=dt_, device=dev).contiguous()
+
+    mu = d(mu0).clone()
+    S = d(S0).clone()
+    B = mu.shape[0]
+    Zt = d(Z)
+    bi = inputs == "batch_inner"
+    if inputs not in ("batch_outer", "batch_inner"):
+        raise ValueError(f"unknown inputs layout {inputs!r}")
+    T, pmax = (Zt.shape[0], Zt.shape[1]) if bi else (Zt.shape[1], Zt.shape[2])
+    if pmax > MAXP:
+        raise ValueError(f"at most {MAXP} measurement rows per step")
+    Ut = d(U)
+    nzt = d(nz, torch.int32)
+    Pt = d(sat_pos)
+    Rt = d(R)
+    Qt = d(Q)
+    shapes = ((T, m, B), (T, B), (T, pmax, q, B), (T, pmax, B)) if bi else \
+        ((B, T, m), (B, T), (B, T, pmax, q), (B, T, pmax))
+    if mu.shape != (B, n) or S.shape != (B, n, n) or Ut.shape != shapes[0] or nzt.shape != shapes[1] \
+            or Pt.shape != shapes[2] or Zt.shape != shapes[3] or Qt.shape != (n, n):
+        raise ValueError("run_batch: inconsistent shapes")
+    if Rt.dim() == 3:
+        r_b, r_s = 0, pmax * pmax
+        if Rt.shape != (T, pmax, pmax):
+            raise ValueError("R must be (T,pmax,pmax) or (B,T,pmax,pmax)")
+    else:
+        r_b, r_s = T * pmax * pmax, pmax * pmax
+        if Rt.shape != (B, T, pmax, pmax):
+            raise ValueError("R must be (T,pmax,pmax) or (B,T,pmax,pmax)")
+    # histories and statistics are written batch-innermost (coalesced device stores) and
+    # returned as (B, T, ...) views of that storage
+    mh_st = torch.empty((T, n, B), dtype=torch.float64, device=dev) if keep_history else None
+    Sh_st = torch.empty((T, n, n, B), dtype=torch.float64, device=dev) if keep_history else None
+    st = torch.empty(B, dtype=torch.int32, device=dev)
+    stats = tuple(torch.empty((T, B), dtype=torch.float64, device=dev) for _ in range(2)) if innovations else ()
+    nis, ll = stats if innovations else (None, None)
+    dims = _lib.MheEkfDims(n=n, m=m, pmax=pmax, q=q, dyn_model=did, meas_model=mid, dt=float(dt),
+                           hist_batch_inner=1, in_batch_inner=int(bi))
+    for i in range(8):
+        dims.dyn_par[i] = float(dp[i])
+    p = _ekf._ptr
+    args = _lib.MheUkfArgs(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
+                           Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
+                           PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
+                           r_bstride=r_b, r_sstride=r_s, mu_hist=p(mh_st), S_hist=p(Sh_st), status=st.data_ptr(),
+                           alpha=alpha, beta=beta, kappa=kappa, nis=p(nis), loglik=p(ll))
+    rc = _lib.load().mhe_ukf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+    _lib.check(rc, "mhe_ukf_run")
+    keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st, *stats)
+    mh = mh_st.permute(2, 0, 1) if keep_history else None
+    Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
+    return (mh, Sh, mu, S, st) + tuple(t.permute(1, 0) for t in stats)
+
+
+class UKF(object):
+    """``utils.ekf.EKF``'s interface on the unscented filter."""
+
+    def __init__(self, dyn_func, meas_func, mu0, S0, alpha=1.0, beta=0.0, kappa=0.0):
+        (_, n, _), _ = _ekf.models(dyn_func, meas_func)  # fail at construction for unregistered plug-ins
+        self.alpha, self.beta, self.kappa = sigma_params(alpha, beta, kappa, n)
+        self.mu = mu0
+        self.S = S0
+        self.dynamics = dyn_func
+        self.measurement = meas_func
+
+    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None):
+        """One predict (+ correct when z is given) step: one launch.  Status 1 raises
+        np.linalg.LinAlgError and leaves mu / S as they were."""
+        meas = meas_func if meas_func is not None else self.measurement
+        (_, n, m), (_, extra, q) = _ekf.models(self.dynamics, meas)
+        dt = float((dyn_func_params or {})["dt"])
+        mu0 = np.asarray(self.mu, dtype=np.float64).reshape(1, n)
+        S0 = np.asarray(self.S, dtype=np.float64).reshape(1, n, n)
+        u_ = np.asarray(u, dtype=np.float64).reshape(1, 1, m)
+        if z is None:
+            pmax, nz = 1, 0
+            Z = np.zeros((1, 1, 1))
+            P = np.zeros((1, 1, 1, q))
+            Rm = np.zeros((1, 1, 1))
+        else:
+            zz = np.atleast_1d(np.asarray(z, dtype=np.float64))
+            nz = pmax = zz.shape[0]
+            Z = zz.reshape(1, 1, pmax)
+            sp = np.asarray(meas_func_params["sat_pos"], dtype=np.float64).reshape(-1, q)
+            if sp.shape[0] + extra != nz:
+                raise ValueError("z and meas_func_params['sat_pos'] disagree in size")
+            P = np.zeros((1, 1, pmax, q))
+            P[0, 0, :sp.shape[0]] = sp
+            Rm = np.asarray(R, dtype=np.float64).reshape(1, pmax, pmax)
+        out = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
+                        np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
+                        dyn_params=dyn_func_params, alpha=self.alpha, beta=self.beta, kappa=self.kappa)
+        mu, S, st = out[2:5]
+        if int(st[0].item()) != 0:
+            raise np.linalg.LinAlgError("a covariance of the unscented filter is not positive definite")
+        self.mu = mu[0].cpu().numpy()
+        self.S = S[0].cpu().numpy()

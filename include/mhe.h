@@ -795,6 +795,58 @@ int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const
                    const double* mu0, const double* S0, double* mu_s, double* S_s, double* mu0_s,
                    double* S0_s, int32_t* status, void* stream);
 
+/*
+ * Unscented fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ukf_run wrote
+ * (added within ABI v11; no existing struct or function changed).  One wavefront per filter, by
+ * the dynamics' VALUES only: no Jacobian enters.  c, wm and wc are mhe_ukf_run's, from the same
+ * (alpha, beta, kappa).  Carrying (mu_s, S_s) of step k+1, which at step steps-1 are the filtered
+ * values, for k = steps-2 .. 0:
+ *   S_k = L L^T                   upper triangle of S_hist read and mirrored; true sqrt and division
+ *   X_0 = mu_k, X_j = mu_k +- c L[:, j]              the forward's sigma points
+ *   Y_j = f(X_j, u_{k+1})                            (history entry k -> k+1 used u_{k+1})
+ *   mu- = sum wm_j Y_j,  S- = sum wc_j (Y_j - mu-)(Y_j - mu-)^T + Q    the forward's expressions
+ *   C   = sum wc_j (X_j - mu_k)(Y_j - mu-)^T         n x n cross covariance
+ *   S-  = L- L-^T,  M = (S-)^-1 C^T                  two triangular solves per column, no inverse
+ *   mu_s[k] = mu_k + M^T (mu_s[k+1] - mu-),  S_s[k] = S_k + M^T (S_s[k+1] - S-) M
+ * Every sum runs in a fixed order (j increasing), so a filter's result is bitwise the same alone
+ * or anywhere in any batch; S_s is computed on its upper triangle and mirrored, so it is bitwise
+ * symmetric.  On the history of a run without corrections (nz = 0 throughout) the recomputed
+ * (mu-, S-) are the history's own next entry, and the call returns that history bitwise.
+ * Of dims this call reads what mhe_ekf_smooth reads; measurements and R do not enter.
+ *   mu_hist, S_hist, U, u_bstride, Q, mu0, S0, mu_s, S_s, mu0_s, S0_s   as mhe_ekf_smooth's (layouts,
+ *                    optional priors, in-place aliasing: a wave has read step k of the input
+ *                    before it writes step k of the output); the smoothed prior is one more
+ *                    step of the recursion from (mu0, S0) with u_0
+ *   alpha, beta, kappa   as mhe_ukf_args', refused alike
+ *   status (B, optional): 0 ok; 1 a pivot of S_k or S- was not positive and finite, or a value
+ *                    written at a step was not finite (a NaN or an infinity in the copied last
+ *                    step or met in the history): that filter's outputs are NaN from the
+ *                    failing step down to step 0 (and its smoothed prior); the steps above it
+ *                    and every other filter are bitwise those of the healthy run.
+ * Stream-ordered: no host synchronisation, no allocation.  Refusals precede any launch and are
+ * mhe_ekf_smooth's, plus mhe_ukf_run's for the struct size and (alpha, beta, kappa)
+ * (batch == 0 or steps == 0: MHE_OK, nothing is read).
+ */
+typedef struct mhe_ukf_smooth_args {
+  int32_t struct_size; /* = sizeof(mhe_ukf_smooth_args) */
+  int32_t batch, steps;
+  const double* mu_hist;
+  const double* S_hist;
+  const double* U;
+  int64_t u_bstride;
+  const double* Q;
+  const double* mu0;
+  const double* S0;
+  double* mu_s;
+  double* S_s;
+  double* mu0_s;
+  double* S0_s;
+  int32_t* status;
+  double alpha, beta, kappa;
+} mhe_ukf_smooth_args;
+
+int mhe_ukf_smooth(const mhe_ekf_dims* dims, const mhe_ukf_smooth_args* args, void* stream);
+
 /* ------------------------------------------------------------------------
  * Batched GNSS least-squares fixes (the MHE initialiser).
  * Replaces utils/leastsquares.py:19-42 (iterativeLeastSquares),

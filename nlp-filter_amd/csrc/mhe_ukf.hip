@@ -331,6 +331,247 @@ int launch(const UkfArgs& a, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
+// ---------------------------------------------------------------- unscented RTS smoother
+// Backward pass over the history k_ukf wrote (include/mhe.h states the recursion), in k_ukf's
+// launch shape: one wavefront per filter, NWF per workgroup, per-wave LDS scratch, wave
+// barriers and wavefront fences between phases, no workgroup barrier.  Carrying the smoothed
+// (mu_s, S_s) of step k+1, step k redoes the forward's prediction from (mu_k, S_k) with
+// u_{k+1} -- k_ukf's expressions term by term, so that on a predict-only history (mu-, S-) are
+// the history's own entry k+1 bitwise -- and adds the cross covariance C of the same points.
+//   * M = S-^-1 C^T: column r of C^T (row r of C) per lane in registers, L- read from LDS
+//     (every lane the same address); forward then backward substitution, sums over t
+//     increasing, times 1 / L-_ii (one true division per pivot, in lane i, broadcast by
+//     v_readlane).  The rows are stored back as G = M^T.
+//   * S_s = S_k + G (S_s' - S-) G^T as E = D G^T (n^2 entries over the lanes) and then the
+//     upper triangle of S_k + G E, one entry per lane, mirrored: bitwise symmetric.
+//   * step k-1's mu, S (upper triangle) and u are loaded into registers before step k's
+//     arithmetic and reach LDS at the top of the next iteration: a wave has read step k of the
+//     input before it writes step k of the output, so the outputs may alias the inputs.
+// The prior, when a smoothed prior is asked for, is one more iteration at k = -1 with u_0.
+struct UrtsArgs {
+  int batch, steps;
+  double dt;
+  double dp[8];
+  double c, wm0, wc0, wi;  // as UkfArgs
+  const double* mu_hist;
+  const double* S_hist;
+  const double* U;
+  long long u_bstride, es;  // as UkfArgs
+  const double* Q;
+  const double* mu0;  // (B, n) / (B, n, n), batch outermost; read only when a smoothed prior is asked for
+  const double* S0;
+  double* mu_s;
+  double* S_s;
+  double* mu0_s;
+  double* S0_s;
+  int hist_bi;
+  int* status;
+};
+
+// element e of step k's w-entry record of filter b; k = -1 is the prior's (B, w) array
+__device__ __forceinline__ size_t urts_at(const UrtsArgs& a, int b, int k, int e, int w) {
+  if (k < 0) return (size_t)b * w + e;
+  return a.hist_bi ? ((size_t)k * w + e) * a.batch + b : ((size_t)b * a.steps + k) * w + e;
+}
+
+// per-wave LDS scratch (doubles): MU mu_k, MP mu-, XM the carried mu_s, DV mu_s' - mu-;
+// A S_k and then its factor L, then E; SK S_k; SP S- and then its factor; CS the carried S_s,
+// then D = S_s' - S-, then the new S_s; C the cross covariance and then G; XS the points Y_j
+template <int n>
+struct RtsSmem {
+  static constexpr int NS = 2 * n + 1;
+  static constexpr int MU = 0, MP = MU + n, XM = MP + n, DV = XM + n, A = DV + n, SK = A + n * n, SP = SK + n * n,
+                       CS = SP + n * n, C = CS + n * n, XS = C + n * n, total = XS + NS * n;
+};
+
+#define URTS_PHASE()                 \
+  __builtin_amdgcn_wave_barrier();   \
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
+
+// waves per SIMD: the n = 9 instance fits 168 VGPRs without a spill, which is three waves
+template <class DYN>
+__global__ __launch_bounds__(NWF * 64) __attribute__((amdgpu_waves_per_eu(3))) void k_ukf_rts(UrtsArgs a) {
+  constexpr int n = DYN::n, m = DYN::m;
+  using WS = RtsSmem<n>;
+  constexpr int NS = WS::NS, NT = n * (n + 1) / 2;
+  static_assert(NT <= 64 && NS <= 64, "one triangle entry and one sigma point per lane");
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int b = blockIdx.x * NWF + wave;
+  if (b >= a.batch) return;  // whole wave exits; no workgroup barrier is used below
+  double* sw = smem + wave * WS::total;
+  double* MU = sw + WS::MU;
+  double* MP = sw + WS::MP;
+  double* XM = sw + WS::XM;
+  double* DV = sw + WS::DV;
+  double* A = sw + WS::A;
+  double* SK = sw + WS::SK;
+  double* SP = sw + WS::SP;
+  double* CS = sw + WS::CS;
+  double* C = sw + WS::C;
+  double* XS = sw + WS::XS;
+  const int kmin = (a.mu0_s || a.S0_s) ? -1 : 0;
+  int tr = 0, tc = 0;  // this lane's entry of an upper triangle
+  if (lane < NT) tri_rc(lane, n, tr, tc);
+  bool bad = false;
+  // what a lane holds of a step's input: mu[lane], S[tr, tc] and the controls of the step after it
+  double pm = 0.0, ps = 0.0, pu[m > 0 ? m : 1] = {};
+  auto load = [&](int k) {
+    const double* hm = k < 0 ? a.mu0 : a.mu_hist;
+    const double* hs = k < 0 ? a.S0 : a.S_hist;
+    if (lane < n) pm = hm[urts_at(a, b, k, lane, n)];
+    if (lane < NT) ps = hs[urts_at(a, b, k, tr * n + tc, n * n)];
+    for (int c = 0; c < m; ++c) pu[c] = a.U[(long long)b * a.u_bstride + ((long long)(k + 1) * m + c) * a.es];
+  };
+  auto store = [&](int k) {  // the carry (XM, CS) is smoothed step k
+    double* om = k < 0 ? a.mu0_s : a.mu_s;
+    double* os = k < 0 ? a.S0_s : a.S_s;
+    if (om)
+      for (int t = lane; t < n; t += 64) om[urts_at(a, b, k, t, n)] = XM[t];
+    if (os)
+      for (int t = lane; t < n * n; t += 64) os[urts_at(a, b, k, t, n * n)] = CS[t];
+  };
+  {  // k = T-1: the smoothed values are the filtered ones
+    const int k = a.steps - 1;
+    if (lane < n) pm = a.mu_hist[urts_at(a, b, k, lane, n)];
+    if (lane < NT) ps = a.S_hist[urts_at(a, b, k, tr * n + tc, n * n)];
+    double vm = pm, vs = ps;
+    bad = __any(!(fabs(vm) < INFINITY) || !(fabs(vs) < INFINITY));
+    if (bad) vm = vs = NAN;
+    if (lane < n) XM[lane] = vm;
+    if (lane < NT) {
+      CS[tr * n + tc] = vs;
+      CS[tc * n + tr] = vs;
+    }
+    if (k - 1 >= kmin) load(k - 1);  // else no step follows (and U has no u_{k+1})
+    URTS_PHASE();
+    store(k);
+  }
+  for (int k = a.steps - 2; k >= kmin; --k) {
+    if (lane < n) MU[lane] = pm;
+    if (lane < NT) {
+      A[tr * n + tc] = ps;
+      A[tc * n + tr] = ps;
+      SK[tr * n + tc] = ps;
+      SK[tc * n + tr] = ps;
+    }
+    double u[m > 0 ? m : 1];
+    for (int c = 0; c < m; ++c) u[c] = pu[c];
+    if (k - 1 >= kmin) load(k - 1);  // arrives under this step's arithmetic
+    URTS_PHASE();
+    // ---- the forward's prediction: sigma points of (mu_k, S_k), one per lane, through the dynamics
+    bool ok = chol_inplace<n>(A, lane);
+    URTS_PHASE();
+    if (lane < NS) {
+      double x[n], xp[n];
+      sigma_point<n>(MU, A, a.c, lane, x);
+      DYN::f(x, u, a.dt, a.dp, xp);
+      for (int c = 0; c < n; ++c) XS[lane * n + c] = xp[c];
+    }
+    URTS_PHASE();
+    if (lane < n) {  // mu- = sum wm_j Y_j
+      double acc = a.wm0 * XS[lane];
+      for (int j = 1; j < NS; ++j) acc += a.wi * XS[j * n + lane];
+      MP[lane] = acc;
+    }
+    URTS_PHASE();
+    for (int t = lane; t < n * (n + 1) / 2; t += 64) {  // S- = sum wc_j (Y_j - mu-)(Y_j - mu-)^T + Q
+      int r, c;
+      tri_rc(t, n, r, c);
+      const double mr = MP[r], mc = MP[c];
+      double acc = a.wc0 * ((XS[r] - mr) * (XS[c] - mc));
+      for (int j = 1; j < NS; ++j) acc += a.wi * ((XS[j * n + r] - mr) * (XS[j * n + c] - mc));
+      acc += a.Q[r * n + c];
+      SP[r * n + c] = acc;
+      SP[c * n + r] = acc;
+      const double dv = CS[r * n + c] - acc;  // D = S_s' - S-, over the carry (bitwise symmetric as both are)
+      CS[r * n + c] = dv;
+      CS[c * n + r] = dv;
+    }
+    for (int t = lane; t < n * n; t += 64) {  // C = sum wc_j (X_j - mu_k)(Y_j - mu-)^T, X_j the points above
+      const int r = t / n, c = t - r * n;
+      const double xr = MU[r], mc = MP[c];
+      double acc = a.wc0 * ((xr - xr) * (XS[c] - mc));
+      for (int j = 1; j <= n; ++j) acc += a.wi * (((xr + a.c * A[r * n + j - 1]) - xr) * (XS[j * n + c] - mc));
+      for (int j = 1; j <= n; ++j) acc += a.wi * (((xr - a.c * A[r * n + j - 1]) - xr) * (XS[(n + j) * n + c] - mc));
+      C[t] = acc;
+    }
+    if (lane < n) DV[lane] = XM[lane] - MP[lane];
+    URTS_PHASE();
+    ok &= chol_inplace<n>(SP, lane);
+    URTS_PHASE();
+    // 1 / L-_ii: one division in lane i, broadcast, so that the substitutions below multiply
+    const double rdl = 1.0 / SP[(lane < n ? lane : 0) * (n + 1)];
+    double rd[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) rd[i] = readlane_d(rdl, i);
+    if (lane < n) {  // L- y = C[lane, :]^T, L-^T g = y: row `lane` of G = C S-^-1
+      double v[n];
+#pragma unroll
+      for (int i = 0; i < n; ++i) v[i] = C[lane * n + i];
+#pragma unroll
+      for (int i = 0; i < n; ++i) {
+        double s = v[i];
+#pragma unroll
+        for (int t = 0; t < i; ++t) s -= SP[i * n + t] * v[t];
+        v[i] = s * rd[i];
+      }
+#pragma unroll
+      for (int i = n - 1; i >= 0; --i) {
+        double s = v[i];
+#pragma unroll
+        for (int t = i + 1; t < n; ++t) s -= SP[t * n + i] * v[t];
+        v[i] = s * rd[i];
+      }
+#pragma unroll
+      for (int i = 0; i < n; ++i) C[lane * n + i] = v[i];
+    }
+    URTS_PHASE();
+    for (int t = lane; t < n * n; t += 64) {  // E = D G^T
+      const int i = t / n, c = t - i * n;
+      double acc = 0.0;
+      for (int j = 0; j < n; ++j) acc += CS[i * n + j] * C[c * n + j];
+      A[t] = acc;
+    }
+    URTS_PHASE();
+    // mu_s = mu_k + G (mu_s' - mu-);  S_s = S_k + G E (upper triangle, mirrored)
+    double vm = 0.0, vs = 0.0;
+    if (lane < n) {
+      double acc = 0.0;
+      for (int i = 0; i < n; ++i) acc += C[lane * n + i] * DV[i];
+      vm = MU[lane] + acc;
+    }
+    if (lane < NT) {
+      double acc = 0.0;
+      for (int i = 0; i < n; ++i) acc += C[tr * n + i] * A[i * n + tc];
+      vs = SK[tr * n + tc] + acc;
+    }
+    // a failed filter is NaN from the failing step down; a non-finite value (one met in the
+    // history, or the carry of a failed step) is a failure as well
+    bad |= !ok;
+    bad |= (bool)__any(!(fabs(vm) < INFINITY) || !(fabs(vs) < INFINITY));
+    if (bad) vm = vs = NAN;
+    if (lane < n) XM[lane] = vm;
+    if (lane < NT) {
+      CS[tr * n + tc] = vs;
+      CS[tc * n + tr] = vs;
+    }
+    URTS_PHASE();
+    store(k);
+  }
+  if (a.status && lane == 0) a.status[b] = bad ? 1 : 0;
+}
+
+#undef URTS_PHASE
+
+template <class DYN>
+int launch_rts(const UrtsArgs& a, hipStream_t st) {
+  const int smem = NWF * RtsSmem<DYN::n>::total * (int)sizeof(double);
+  hipLaunchKernelGGL((k_ukf_rts<DYN>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
+  return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
+}
+
 }  // namespace mhe_ukf
 
 extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream) {
@@ -382,6 +623,52 @@ extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, v
   if (dims->in_batch_inner) {  // U (steps, m, B), Z (steps, pmax, B), nz (steps, B), PAR (steps, pmax, q, B)
     a.es = batch;
     a.u_bstride = a.z_bstride = a.nz_bstride = a.par_bstride = 1;
+  }
+  return run(a, (hipStream_t)stream);
+}
+
+extern "C" int mhe_ukf_smooth(const mhe_ekf_dims* dims, const mhe_ukf_smooth_args* args, void* stream) {
+  using namespace mhe_ukf;
+  using namespace mhe_ekf;
+  if (!dims || !args) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ukf_smooth_args)) return MHE_ERR_DIMS;
+  const double al = args->alpha, be = args->beta, ka = args->kappa;  // mhe_ukf_run's conditions
+  if (!(al > 0.0 && al < INFINITY) || !(fabs(be) < INFINITY) || !(fabs(ka) < INFINITY)) return MHE_ERR_DIMS;
+  const double nn = (double)dims->n;
+  if (!(nn + ka > 0.0)) return MHE_ERR_DIMS;
+  const double lam = al * al * (nn + ka) - nn;
+  if (!(nn + lam > 0.0 && nn + lam < INFINITY)) return MHE_ERR_DIMS;
+  const int32_t batch = args->batch, steps = args->steps;
+  if (batch < 0 || steps < 0) return MHE_ERR_DIMS;
+  if (batch == 0 || steps == 0) return MHE_OK;
+  int (*run)(const UrtsArgs&, hipStream_t) = nullptr;
+  if (dims->dyn_model == MHE_EKF_DYN_GNSS_POS_AND_BIAS) {
+    if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
+    run = launch_rts<EkfGnssPosAndBias>;
+  } else if (dims->dyn_model == MHE_EKF_DYN_DISCRETE_VEHICLE) {
+    if (dims->n != 9 || dims->m != 2) return MHE_ERR_MODEL;
+    if (!(dims->dyn_par[2] != 0.0 && dims->dyn_par[5] != 0.0)) return MHE_ERR_DIMS;  // M, I_Z unset
+    run = launch_rts<EkfDiscreteVehicle>;
+  } else {
+    return MHE_ERR_MODEL;
+  }
+  if (!args->mu_hist || !args->S_hist || !args->U || !args->Q || !args->mu_s || !args->S_s) return MHE_ERR_NULL;
+  if ((args->mu0_s || args->S0_s) && (!args->mu0 || !args->S0)) return MHE_ERR_NULL;
+  UrtsArgs a = {};
+  a.batch = batch; a.steps = steps; a.dt = dims->dt;
+  for (int i = 0; i < 8; ++i) a.dp[i] = dims->dyn_par[i];
+  a.c = sqrt(nn + lam);  // the weights as mhe_ukf_run forms them
+  a.wm0 = lam / (nn + lam);
+  a.wc0 = a.wm0 + 1.0 - al * al + be;
+  a.wi = 1.0 / (2.0 * (nn + lam));
+  a.mu_hist = args->mu_hist; a.S_hist = args->S_hist; a.U = args->U; a.u_bstride = args->u_bstride; a.es = 1;
+  a.Q = args->Q; a.mu0 = args->mu0; a.S0 = args->S0; a.mu_s = args->mu_s; a.S_s = args->S_s;
+  a.mu0_s = args->mu0_s; a.S0_s = args->S0_s; a.status = args->status;
+  a.hist_bi = dims->hist_batch_inner != 0;
+  if (dims->in_batch_inner) {  // U (steps, m, B)
+    a.es = batch;
+    a.u_bstride = 1;
   }
   return run(a, (hipStream_t)stream);
 }

@@ -66,6 +66,13 @@ class MheUkfArgs(_Sized):
                 ("beta", c_dbl), ("kappa", c_dbl), ("nis", c_vp), ("loglik", c_vp)]
 
 
+class MheUkfSmoothArgs(_Sized):
+    _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu_hist", c_vp), ("S_hist", c_vp),
+                ("U", c_vp), ("u_bstride", c_i64), ("Q", c_vp), ("mu0", c_vp), ("S0", c_vp), ("mu_s", c_vp),
+                ("S_s", c_vp), ("mu0_s", c_vp), ("S0_s", c_vp), ("status", c_vp), ("alpha", c_dbl),
+                ("beta", c_dbl), ("kappa", c_dbl)]
+
+
 class MheLsDims(_Sized):
     _fields_ = [("struct_size", c_i32), ("slots", c_i32), ("max_iter", c_i32), ("warm", c_i32), ("with_vel", c_i32), ("tol", c_dbl)]
 
@@ -131,6 +138,7 @@ SIGNATURES = {
     "mhe_ukf_run": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfArgs), c_vp]),
     "mhe_ekf_smooth": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp]),
+    "mhe_ukf_smooth": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfSmoothArgs), c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp]),
     "mhe_ls_multi_run": (ctypes.c_int, [_PM, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -19,8 +19,12 @@ centre weight is about -1e6 and the weighted sums cancel at that magnitude: in f
 the rounding floor of the gnss position rose from 1.6e-6 m to 1.6e-3 m.  alpha, beta and
 kappa remain parameters.
 
-Not formed: innovation gating, a filter-per-lane kernel, an unscented RTS pass
-(``utils.ekf.smooth_batch`` over a UKF history is the EKF-linearised smoother).
+``smooth_batch`` is the unscented fixed-interval (RTS) smoother over the history
+``run_batch`` returns (``mhe_ukf_smooth``, k_ukf_rts): the backward pass by the same sigma
+points and the dynamics' values.  ``utils.ekf.smooth_batch`` over a UKF history is the
+EKF-linearised smoother instead, which puts the hand-written Jacobians back in.
+
+Not formed: innovation gating, a filter-per-lane kernel, two filters per wave.
 """
 import ctypes
 import math
@@ -149,6 +153,76 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     mh = mh_st.permute(2, 0, 1) if keep_history else None
     Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
     return (mh, Sh, mu, S, st) + tuple(t.permute(1, 0) for t in stats)
+
+
+def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_params=None, inputs="batch_outer",
+                 alpha=1.0, beta=0.0, kappa=0.0, device=None, stream=None):
+    """Unscented fixed-interval (Rauch-Tung-Striebel) smoother over a filtered history, B
+    filters in one launch of ``mhe_ukf_smooth`` (one wavefront per filter; include/mhe.h
+    states the recursion).  The backward pass redoes the forward's prediction from the
+    dynamics' values and the same sigma points: no Jacobian enters.
+
+    Arguments, shapes, layouts and ``stream`` are ``utils.ekf.smooth_batch``'s: mu_hist (B,T,n),
+    S_hist (B,T,n,n) as ``run_batch`` returned them (its batch-innermost views go to the kernel
+    without a copy), U (B,T,m) -- or (T,m,B) with inputs="batch_inner" -- Q (n,n), dt and
+    dyn_params as given to ``run_batch``; mu0 (B,n), S0 (B,n,n) optionally the prior the filter
+    started from.  alpha, beta, kappa: the forward run's (a bad value raises ValueError).
+    Returns (mu_s (B,T,n), S_s (B,T,n,n), status (B)) and, with a prior, also (mu0_s (B,n),
+    S0_s (B,n,n)); S_s is bitwise symmetric.  status 1: a Cholesky pivot of S_k or of the
+    predicted covariance was not positive and finite, or the history held a non-finite value;
+    that filter is NaN from the failing step down, no other filter is touched."""
+    did, n, m = _ekf.dynamics(dyn_func)
+    alpha, beta, kappa = sigma_params(alpha, beta, kappa, n)
+    if dyn_params is not None and "dt" in dyn_params:
+        dt = dyn_params["dt"]
+    if inputs not in ("batch_outer", "batch_inner"):
+        raise ValueError(f"unknown inputs layout {inputs!r}")
+    if (mu0 is None) != (S0 is None):
+        raise ValueError("smooth_batch: mu0 and S0 go together")
+    bi = inputs == "batch_inner"
+    shp = lambda a: tuple(a.shape)   # noqa: E731
+    if len(shp(mu_hist)) != 3 or len(shp(S_hist)) != 4:
+        raise ValueError("smooth_batch: mu_hist must be (B,T,n) and S_hist (B,T,n,n)")
+    B, T = shp(mu_hist)[:2]
+    if shp(mu_hist) != (B, T, n) or shp(S_hist) != (B, T, n, n) or shp(Q) != (n, n) \
+            or shp(U) != ((T, m, B) if bi else (B, T, m)) \
+            or (mu0 is not None and (shp(mu0) != (B, n) or shp(S0) != (B, n, n))):
+        raise ValueError("smooth_batch: inconsistent shapes")
+    _ekf.verify_dynamics(dyn_func, dict(dyn_params or {}, dt=dt))
+    dp = _ekf.dyn_par(dyn_func, dyn_params)
+    import torch
+
+    from mhe.streams import keep_alive, launch_stream
+
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with launch_stream(stream, dev) as (s, cur):
+        def d(a):
+            return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=torch.float64, device=dev)
+
+        mh, mh_bi = _ekf._hist_storage(d(mu_hist), (n,))
+        Sh, Sh_bi = _ekf._hist_storage(d(S_hist), (n, n))
+        if mh_bi != Sh_bi:   # one layout flag covers both histories
+            mh, Sh, mh_bi = d(mu_hist).contiguous(), d(S_hist).contiguous(), False
+        Ut, Qt = d(U).contiguous(), d(Q).contiguous()
+        prior = mu0 is not None
+        m0, S0t = (d(mu0).contiguous(), d(S0).contiguous()) if prior else (None, None)
+        ms, Ss = torch.empty_like(mh), torch.empty_like(Sh)
+        m0s, S0s = (torch.empty_like(m0), torch.empty_like(S0t)) if prior else (None, None)
+        st = torch.empty(B, dtype=torch.int32, device=dev)
+        dims = _lib.MheEkfDims(n=n, m=m, dyn_model=did, dt=float(dt), hist_batch_inner=int(mh_bi),
+                               in_batch_inner=int(bi))
+        for i in range(8):
+            dims.dyn_par[i] = float(dp[i])
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        args = _lib.MheUkfSmoothArgs(batch=B, steps=T, mu_hist=p(mh), S_hist=p(Sh), U=p(Ut), u_bstride=T * m,
+                                     Q=p(Qt), mu0=p(m0), S0=p(S0t), mu_s=p(ms), S_s=p(Ss), mu0_s=p(m0s),
+                                     S0_s=p(S0s), status=p(st), alpha=alpha, beta=beta, kappa=kappa)
+        rc = _lib.load().mhe_ukf_smooth(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ukf_smooth")
+        keep_alive(s, cur, mh, Sh, Ut, Qt, m0, S0t, ms, Ss, m0s, S0s, st)
+        if mh_bi:
+            ms, Ss = ms.permute(2, 0, 1), Ss.permute(3, 0, 1, 2)
+        return (ms, Ss, st, m0s, S0s) if prior else (ms, Ss, st)
 
 
 class UKF(object):

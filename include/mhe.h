@@ -766,6 +766,59 @@ typedef struct mhe_ukf_args {
 int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream);
 
 /*
+ * Innovation gating and a rejection mask for the unscented filter (added within v11; no existing
+ * struct or function changed).  mhe_ukf_gate_args holds mhe_ukf_args' fields in order, then:
+ *   gate    0: no screening.  > 0 (+inf allowed, screens nothing): at a step with 0 < nz <= pmax,
+ *           after e and Pzz (R included) are formed from the redrawn sigma points,
+ *               d2_i = e_i^2 / Pzz_ii   (i < nz)
+ *           and row i is screened out iff d2_i > gate.  A NaN or non-positive Pzz_ii keeps the
+ *           row (status 1 then reports it through the pivot, as for the EKF).  The screen is
+ *           marginal and taken at the prediction: it depends neither on the row order nor on
+ *           the other rows.  The correction is the one above over the kept rows, in their order,
+ *           with the kept sub-blocks of Pzz and Pxz.  Every entry of e, Pzz and Pxz is a sum
+ *           over the sigma points of that row's own values, so the result is exactly the
+ *           ungated filter fed only the kept rows.  Rows keep their index: the bias row of
+ *           MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS stays row nz-1, keeps h = x[3] and is
+ *           screened like any other.  A step whose rows are all screened out is predict-only:
+ *           mu = mu-, S = S-, nis = loglik = 0.  NaN or negative: MHE_ERR_DIMS.
+ *   rej     optional per-step output laid out as nis / loglik ((steps, B) with
+ *           dims->hist_batch_inner, else (B, steps)): bit i is set iff row i was screened out
+ *           (pmax <= 32: bit 31 is a row like any other); 0 on a step with nz = 0 or nz > pmax.
+ * With a gate, nis and loglik are taken over the kept rows a: nis = w^T w and
+ * loglik = -(nis + 2 sum_a log L_ii + |a| log 2 pi) / 2.  The status rules are mhe_ukf_run's.
+ * gate == 0 with rej NULL runs exactly what mhe_ukf_run runs; refusals and return codes are
+ * mhe_ukf_run's (a NULL or wrongly sized args struct is refused like dims; batch == 0 or
+ * steps == 0: MHE_OK, nothing is read).
+ */
+typedef struct mhe_ukf_gate_args {
+  int32_t struct_size; /* = sizeof(mhe_ukf_gate_args) */
+  int32_t batch, steps;
+  double* mu;
+  double* S;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const double* Q;
+  const double* R;
+  int64_t r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int32_t* status;
+  double alpha, beta, kappa;
+  double* nis;
+  double* loglik;
+  double gate;
+  int32_t* rej;
+} mhe_ukf_gate_args;
+
+int mhe_ukf_run_gated(const mhe_ekf_dims* dims, const mhe_ukf_gate_args* args, void* stream);
+
+/*
  * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
  * (added to ABI v11; no existing struct or function changed).  One filter per lane;
  * a filter's result does not depend on the batch or on its place in it.

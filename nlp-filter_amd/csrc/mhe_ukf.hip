@@ -13,9 +13,12 @@
 //     lane-iteration, each summed over j = 0 .. 2n in that order.
 //   * the correction is k_ekf's augmented right-looking sweep, here over [Pzz | Pxz^T | e]:
 //     Y = L^-1 Pxz^T, w = L^-1 e, mu = mu- + Y^T w, S = S- - Y^T Y.
+//   * k_ukf<.., GATE = true> screens the rows on e_i^2 / Pzz_ii before the sweep (mhe_ukf_run_gated).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "mhe.h"
 #include "mhe_ekf_models.h"
@@ -55,6 +58,20 @@ struct UkfArgs {
   double* nis;   // per-step statistics, optional: (steps, B) with hist_bi, else (B, steps)
   double* loglik;
 };
+
+// the gated instances (k_ukf<.., true>) take these as well; the others keep the kernel
+// arguments they had
+struct UkfGateArgs : UkfArgs {
+  double gate;  // screen threshold on d2_i = e_i^2 / Pzz_ii; +inf: no screening
+  int* rej;     // optional, laid out as nis: bit i = row i was screened out
+};
+template <bool GATE>
+struct KArgs { using type = UkfArgs; };
+template <>
+struct KArgs<true> { using type = UkfGateArgs; };
+
+// bits 0..rows-1 (rows <= 32)
+__device__ __forceinline__ unsigned row_bits(int rows) { return rows >= 32 ? 0xffffffffu : (1u << rows) - 1u; }
 
 // element (b, k, e) of a per-step history with `w` entries per step
 __device__ __forceinline__ size_t hist_at(const UkfArgs& a, int b, int k, int e, int w) {
@@ -129,8 +146,16 @@ __device__ __forceinline__ void sigma_point(const double* mean, const double* L,
   for (int r = 0; r < n; ++r) x[r] = j == 0 ? mean[r] : mean[r] + sc * L[r * n + col];
 }
 
-template <class DYN, class MEAS>
-__global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
+// GATE: innovation screening (include/mhe.h states it).  Lane i holds e_i and reads Pzz_ii
+// from PZ once the phase that writes PZ is over; row i is screened out iff
+// e_i^2 / Pzz_ii > a.gate (a NaN or non-positive Pzz_ii keeps the row, and the pivot test then
+// reports it).  The kept rows are a wave-uniform ballot mask.  A screened lane holds a zero row
+// of [Pzz | Pxz^T | e] and is never a pivot, so the kept lanes run the sweep of the kept
+// sub-blocks in their order and the screened rows of Y and w are exact zeros in the two closing
+// sums: the step is the ungated one fed the kept rows only.  No kept row: predict-only.
+// GATE = false is the code as it was: those instances serve every call without gate and rej.
+template <class DYN, class MEAS, bool GATE = false>
+__global__ __launch_bounds__(NWF * 64) void k_ukf(typename KArgs<GATE>::type a) {
   constexpr int n = DYN::n, m = DYN::m, q = MEAS::q;
   using WS = WaveSmem<n>;
   constexpr int NS = WS::NS;
@@ -185,6 +210,7 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
     UKF_PHASE();
     const int nz = a.nz[(long long)b * a.nz_bstride + (long long)k * a.es];
     double nis = 0.0, loglik = 0.0;
+    unsigned rejm = 0;  // GATE: the step's screened rows
     // Z / PAR / R hold pmax (<= MAXP) rows per step: a step that claims more is refused
     if (nz > 0 && nz <= a.nmeas_rows_max) {
       // ---- sigma points redrawn from (mu-, S-)
@@ -234,7 +260,16 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
       UKF_PHASE();
       // ---- augmented sweep: lane i holds row i of [Pzz | Pxz^T | e]
       const int i = lane;
-      const bool row = i < nz;
+      bool row = i < nz;
+      unsigned km = 0xffffffffu;  // GATE: the kept rows (wave-uniform)
+      if constexpr (GATE) {
+        const double pd = row ? PZ[tri_at(i, i)] : 0.0;  // nz <= MAXP: a row's lane is below MAXP
+        const bool keep = row && !(pd > 0.0 && e * e / pd > a.gate);
+        km = (unsigned)__ballot(keep);
+        rejm = ~km & row_bits(nz);
+        if (!keep) e = 0.0;
+        row = keep;  // a screened lane holds no row of the sweep
+      }
       double p[MAXP], t1[n];
 #pragma unroll
       for (int j = 0; j < MAXP; ++j) {
@@ -247,7 +282,7 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
       bool bad = false;
 #pragma unroll
       for (int c = 0; c < MAXP; ++c) {
-        if (c < nz) {
+        if (c < nz && (!GATE || ((km >> c) & 1u))) {
           const double piv = readlane_d(p[c], c);
           bad |= !(piv > 0.0 && piv < INFINITY);
           const double rs = 1.0 / sqrt(piv);
@@ -267,6 +302,10 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
 #pragma unroll
         for (int c = 0; c < n; ++c) T1[i * n + c] = t1[c] * idg;  // Y = L^-1 Pxz^T
         E[i] = e * idg;                                          // w = L^-1 e
+      } else if (GATE && i < nz) {  // a screened row of Y and w: exact zeros for the sums below
+#pragma unroll
+        for (int c = 0; c < n; ++c) T1[i * n + c] = 0.0;
+        E[i] = 0.0;
       }
       if (a.nis || a.loglik) {  // wave-uniform
         // nis = w^T w, sum log L_ii = -sum log(1 / L_ii): the rows sit in lanes 0..31
@@ -278,7 +317,12 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
           lg += __shfl_xor(lg, off);
         }
         nis = s2;
-        loglik = -0.5 * (s2 - 2.0 * lg + nz * LOG_2PI);
+        if constexpr (GATE) {
+          const int cnt = __popc(km);  // rows applied; none: s2 = 0 and loglik = 0
+          loglik = cnt ? -0.5 * (s2 - 2.0 * lg + cnt * LOG_2PI) : 0.0;
+        } else {
+          loglik = -0.5 * (s2 - 2.0 * lg + nz * LOG_2PI);
+        }
       }
       UKF_PHASE();
       // mu = mu- + Y^T w ; S = S- - Y^T Y (upper triangle, mirrored)
@@ -294,7 +338,7 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
       for (int t = lane; t < n; t += 64) {
         double acc = 0.0;
         for (int ii = 0; ii < nz; ++ii) acc += T1[ii * n + t] * E[ii];
-        mu[t] = MP[t] + acc;
+        mu[t] = GATE && km == 0 ? MP[t] : MP[t] + acc;  // every row screened out: mu- itself
       }
     } else {
       if (nz > a.nmeas_rows_max) status = 2;
@@ -311,6 +355,9 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
       const size_t at = hist_at(a, b, k, 0, 1);
       if (a.nis) a.nis[at] = nis;
       if (a.loglik) a.loglik[at] = loglik;
+      if constexpr (GATE) {
+        if (a.rej) a.rej[at] = (int)rejm;
+      }
     }
     if (a.mu_hist)
       for (int t = lane; t < n; t += 64) a.mu_hist[hist_at(a, b, k, t, n)] = mu[t];
@@ -325,9 +372,15 @@ __global__ __launch_bounds__(NWF * 64) void k_ukf(UkfArgs a) {
 #undef UKF_PHASE
 
 template <class DYN, class MEAS>
-int launch(const UkfArgs& a, hipStream_t st) {
+int launch(const UkfGateArgs& g, hipStream_t st, bool gated) {
   const int smem = NWF * WaveSmem<DYN::n>::total * (int)sizeof(double);
-  hipLaunchKernelGGL((k_ukf<DYN, MEAS>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
+  const dim3 grid((g.batch + NWF - 1) / NWF), block(NWF * 64);
+  if (gated) {
+    hipLaunchKernelGGL((k_ukf<DYN, MEAS, true>), grid, block, smem, st, g);
+  } else {
+    const UkfArgs& a = g;
+    hipLaunchKernelGGL((k_ukf<DYN, MEAS, false>), grid, block, smem, st, a);
+  }
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
@@ -574,12 +627,11 @@ int launch_rts(const UrtsArgs& a, hipStream_t st) {
 
 }  // namespace mhe_ukf
 
-extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream) {
+// mhe_ukf_run and mhe_ukf_run_gated behind their struct checks: `args` holds mhe_ukf_args'
+// fields; gate 0 and rej NULL run the instances without the screen
+static int ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, double gate, int32_t* rej, void* stream) {
   using namespace mhe_ukf;
   using namespace mhe_ekf;
-  if (!dims || !args) return MHE_ERR_NULL;
-  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
-  if (args->struct_size != (int32_t)sizeof(mhe_ukf_args)) return MHE_ERR_DIMS;
   const double al = args->alpha, be = args->beta, ka = args->kappa;
   if (!(al > 0.0 && al < INFINITY) || !(fabs(be) < INFINITY) || !(fabs(ka) < INFINITY)) return MHE_ERR_DIMS;
   const double nn = (double)dims->n;
@@ -593,7 +645,7 @@ extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, v
     return MHE_ERR_NULL;
   if (dims->q != 3) return MHE_ERR_DIMS;
   if (!args->PAR) return MHE_ERR_NULL;
-  int (*run)(const UkfArgs&, hipStream_t) = nullptr;
+  int (*run)(const UkfGateArgs&, hipStream_t, bool) = nullptr;
   if (dims->dyn_model == MHE_EKF_DYN_GNSS_POS_AND_BIAS) {
     if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
     if (dims->meas_model == MHE_EKF_MEAS_MULTI_PSEUDORANGE)
@@ -606,7 +658,7 @@ extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, v
     if (dims->meas_model == MHE_EKF_MEAS_VEHICLE_SENSORS) run = launch<EkfDiscreteVehicle, EkfVehicleSensors>;
   }
   if (!run) return MHE_ERR_MODEL;
-  UkfArgs a = {};
+  UkfGateArgs a = {};
   a.batch = batch; a.steps = steps; a.nmeas_rows_max = dims->pmax; a.dt = dims->dt;
   for (int i = 0; i < 8; ++i) a.dp[i] = dims->dyn_par[i];
   a.c = sqrt(nn + lam);
@@ -624,7 +676,28 @@ extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, v
     a.es = batch;
     a.u_bstride = a.z_bstride = a.nz_bstride = a.par_bstride = 1;
   }
-  return run(a, (hipStream_t)stream);
+  a.gate = gate != 0.0 ? gate : INFINITY;
+  a.rej = rej;
+  return run(a, (hipStream_t)stream, gate != 0.0 || rej);
+}
+
+extern "C" int mhe_ukf_run(const mhe_ekf_dims* dims, const mhe_ukf_args* args, void* stream) {
+  if (!dims || !args) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ukf_args)) return MHE_ERR_DIMS;
+  return ukf_run(dims, args, 0.0, nullptr, stream);
+}
+
+extern "C" int mhe_ukf_run_gated(const mhe_ekf_dims* dims, const mhe_ukf_gate_args* args, void* stream) {
+  static_assert(offsetof(mhe_ukf_gate_args, gate) == sizeof(mhe_ukf_args), "mhe_ukf_args' fields, then gate and rej");
+  if (!dims || !args) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ukf_gate_args)) return MHE_ERR_DIMS;
+  if (!(args->gate >= 0.0)) return MHE_ERR_DIMS;  // NaN or negative; 0 = no screening, +inf allowed
+  mhe_ukf_args u;
+  memcpy(&u, args, sizeof u);  // the leading fields are mhe_ukf_args' in order
+  u.struct_size = (int32_t)sizeof u;
+  return ukf_run(dims, &u, args->gate, args->rej, stream);
 }
 
 extern "C" int mhe_ukf_smooth(const mhe_ekf_dims* dims, const mhe_ukf_smooth_args* args, void* stream) {

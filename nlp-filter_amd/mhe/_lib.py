@@ -66,6 +66,10 @@ class MheUkfArgs(_Sized):
                 ("beta", c_dbl), ("kappa", c_dbl), ("nis", c_vp), ("loglik", c_vp)]
 
 
+class MheUkfGateArgs(_Sized):
+    _fields_ = MheUkfArgs._fields_ + [("gate", c_dbl), ("rej", c_vp)]
+
+
 class MheUkfSmoothArgs(_Sized):
     _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu_hist", c_vp), ("S_hist", c_vp),
                 ("U", c_vp), ("u_bstride", c_i64), ("Q", c_vp), ("mu0", c_vp), ("S0", c_vp), ("mu_s", c_vp),
@@ -136,6 +140,7 @@ SIGNATURES = {
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ekf_run_args": (ctypes.c_int, [_PE, ctypes.POINTER(MheEkfArgs), c_vp]),
     "mhe_ukf_run": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfArgs), c_vp]),
+    "mhe_ukf_run_gated": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfGateArgs), c_vp]),
     "mhe_ekf_smooth": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp]),
     "mhe_ukf_smooth": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfSmoothArgs), c_vp]),

@@ -24,7 +24,11 @@ kappa remain parameters.
 points and the dynamics' values.  ``utils.ekf.smooth_batch`` over a UKF history is the
 EKF-linearised smoother instead, which puts the hand-written Jacobians back in.
 
-Not formed: innovation gating, a filter-per-lane kernel, two filters per wave.
+``run_batch(gate=...)`` / ``UKF.update(gate=...)`` screen rows on their normalised innovation
+d2_i = e_i^2 / Pzz_ii as ``utils.ekf`` does and report the rejection mask (``mhe_ukf_run_gated``,
+k_ukf<.., GATE>); without ``gate`` the call is ``mhe_ukf_run``'s and its instances, as before.
+
+Not formed: a filter-per-lane kernel, two filters per wave, joint (chi-square of nz) gating.
 """
 import ctypes
 import math
@@ -60,7 +64,7 @@ def sigma_params(alpha, beta, kappa, n):
 
 def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=None, stream=None,
               keep_history=True, inputs="batch_outer", dyn_params=None, alpha=1.0, beta=0.0, kappa=0.0,
-              innovations=False):
+              innovations=False, **screen):
     """Run B independent unscented filters for T steps in one launch.
 
     Shapes, layouts (``inputs``) and ``stream`` are ``utils.ekf.run_batch``'s: mu0 (B,n),
@@ -75,7 +79,23 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     innovations=True appends (nis (B,T), loglik (B,T)): nis = e^T Pzz^-1 e and
     loglik = -(nis + log det Pzz + nz log 2 pi) / 2, both 0 on a step without a correction.
     alpha, beta, kappa: the scaled unscented transform's parameters (see the module
-    docstring for the defaults); a bad value raises ValueError."""
+    docstring for the defaults); a bad value raises ValueError.
+    gate (keyword only, default None; the named parameters are the ungated call's, which
+    tests/test_ukf_host.py pins): None, or a threshold > 0 on the normalised innovation of each row at the prediction,
+    d2_i = e_i^2 / Pzz_ii with e and Pzz (R included) of the redrawn sigma points: a row with
+    d2_i > gate is screened out and the correction is the usual one over the rows that remain,
+    exactly the ungated filter fed only those rows (none: the step is predict-only).  Rows
+    keep their index.  10.83 is the 0.999 quantile of chi-square with one degree of freedom;
+    np.inf screens nothing.  With a gate, innovations=True appends (nis (B,T), loglik (B,T),
+    rejected (B,T) int32) as ``utils.ekf.run_batch`` does: nis and loglik over the kept rows
+    (0 when no row was applied), bit i of rejected set iff row i was screened out.  A bad
+    gate raises ValueError.  Without ``gate`` the call, the entry point (mhe_ukf_run) and the
+    returned tuple are what they were."""
+    gate = screen.pop("gate", None)
+    if screen:
+        raise TypeError(f"run_batch() got an unexpected keyword argument {next(iter(screen))!r}")
+    gated = gate is not None
+    gate = _ekf._gate_value(gate)
     (did, n, m), (mid, _, q) = _ekf.models(dyn_func, meas_func)
     alpha, beta, kappa = sigma_params(alpha, beta, kappa, n)
     import torch
@@ -89,11 +109,11 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with launch_stream(stream, dev) as (s, cur):
         return _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history,
-                          inputs, dp, alpha, beta, kappa, bool(innovations))
+                          inputs, dp, alpha, beta, kappa, bool(innovations), gate if gated else None)
 
 
 def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history, inputs, dp,
-               alpha, beta, kappa, innovations):
+               alpha, beta, kappa, innovations, gate=None):
     """run_batch on torch stream s (staging and allocation ordered on s)."""
     import torch
 
@@ -135,20 +155,27 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     mh_st = torch.empty((T, n, B), dtype=torch.float64, device=dev) if keep_history else None
     Sh_st = torch.empty((T, n, n, B), dtype=torch.float64, device=dev) if keep_history else None
     st = torch.empty(B, dtype=torch.int32, device=dev)
-    stats = tuple(torch.empty((T, B), dtype=torch.float64, device=dev) for _ in range(2)) if innovations else ()
-    nis, ll = stats if innovations else (None, None)
+    kinds = (torch.float64, torch.float64) + ((torch.int32,) if gate is not None else ())
+    stats = tuple(torch.empty((T, B), dtype=dt_, device=dev) for dt_ in kinds) if innovations else ()
+    nis, ll, rej = (stats + (None,))[:3] if innovations else (None, None, None)
     dims = _lib.MheEkfDims(n=n, m=m, pmax=pmax, q=q, dyn_model=did, meas_model=mid, dt=float(dt),
                            hist_batch_inner=1, in_batch_inner=int(bi))
     for i in range(8):
         dims.dyn_par[i] = float(dp[i])
     p = _ekf._ptr
-    args = _lib.MheUkfArgs(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
-                           Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
-                           PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
-                           r_bstride=r_b, r_sstride=r_s, mu_hist=p(mh_st), S_hist=p(Sh_st), status=st.data_ptr(),
-                           alpha=alpha, beta=beta, kappa=kappa, nis=p(nis), loglik=p(ll))
-    rc = _lib.load().mhe_ukf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
-    _lib.check(rc, "mhe_ukf_run")
+    fields = dict(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
+                  Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
+                  PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
+                  r_bstride=r_b, r_sstride=r_s, mu_hist=p(mh_st), S_hist=p(Sh_st), status=st.data_ptr(),
+                  alpha=alpha, beta=beta, kappa=kappa, nis=p(nis), loglik=p(ll))
+    if gate is None:
+        args = _lib.MheUkfArgs(**fields)
+        rc = _lib.load().mhe_ukf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ukf_run")
+    else:
+        args = _lib.MheUkfGateArgs(gate=gate, rej=p(rej), **fields)
+        rc = _lib.load().mhe_ukf_run_gated(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ukf_run_gated")
     keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st, *stats)
     mh = mh_st.permute(2, 0, 1) if keep_history else None
     Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
@@ -170,7 +197,9 @@ def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_par
     Returns (mu_s (B,T,n), S_s (B,T,n,n), status (B)) and, with a prior, also (mu0_s (B,n),
     S0_s (B,n,n)); S_s is bitwise symmetric.  status 1: a Cholesky pivot of S_k or of the
     predicted covariance was not positive and finite, or the history held a non-finite value;
-    that filter is NaN from the failing step down, no other filter is touched."""
+    that filter is NaN from the failing step down, no other filter is touched.
+    Measurements do not enter the backward pass, so the history of a gated run (run_batch's
+    ``gate``) smooths as any other."""
     did, n, m = _ekf.dynamics(dyn_func)
     alpha, beta, kappa = sigma_params(alpha, beta, kappa, n)
     if dyn_params is not None and "dt" in dyn_params:
@@ -236,9 +265,15 @@ class UKF(object):
         self.dynamics = dyn_func
         self.measurement = meas_func
 
-    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None):
+    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None, gate=None):
         """One predict (+ correct when z is given) step: one launch.  Status 1 raises
-        np.linalg.LinAlgError and leaves mu / S as they were."""
+        np.linalg.LinAlgError and leaves mu / S as they were.
+
+        gate (run_batch's; np.inf: statistics only): rows of z whose normalised innovation
+        exceeds it are left out of the correction, and the object then holds ``nis``,
+        ``loglik`` (floats) and ``rejected`` (bool, one per row of z) of this update.
+        Without a gate nothing changes."""
+        gv = _ekf._gate_value(gate)
         meas = meas_func if meas_func is not None else self.measurement
         (_, n, m), (_, extra, q) = _ekf.models(self.dynamics, meas)
         dt = float((dyn_func_params or {})["dt"])
@@ -260,11 +295,16 @@ class UKF(object):
             P = np.zeros((1, 1, pmax, q))
             P[0, 0, :sp.shape[0]] = sp
             Rm = np.asarray(R, dtype=np.float64).reshape(1, pmax, pmax)
+        kw = {} if gate is None else dict(gate=gv, innovations=True)
         out = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
                         np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
-                        dyn_params=dyn_func_params, alpha=self.alpha, beta=self.beta, kappa=self.kappa)
+                        dyn_params=dyn_func_params, alpha=self.alpha, beta=self.beta, kappa=self.kappa, **kw)
         mu, S, st = out[2:5]
         if int(st[0].item()) != 0:
             raise np.linalg.LinAlgError("a covariance of the unscented filter is not positive definite")
+        if gate is not None:
+            self.nis, self.loglik = float(out[5][0, 0].item()), float(out[6][0, 0].item())
+            word = int(out[7][0, 0].item()) & 0xFFFFFFFF
+            self.rejected = np.array([bool((word >> i) & 1) for i in range(nz)], dtype=bool)
         self.mu = mu[0].cpu().numpy()
         self.S = S[0].cpu().numpy()

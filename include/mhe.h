@@ -819,6 +819,67 @@ typedef struct mhe_ukf_gate_args {
 int mhe_ukf_run_gated(const mhe_ekf_dims* dims, const mhe_ukf_gate_args* args, void* stream);
 
 /*
+ * Iterated extended Kalman filter (added within v11; no existing struct or function changed).
+ * The Gauss-Newton solve of each step's MAP problem
+ *   min_x (x - mu-)^T S-^-1 (x - mu-) + (z - h(x))^T R^-1 (z - h(x)):
+ * the measurement model is relinearised at the current iterate and the correction of
+ * mhe_ekf_run is redone from the prediction.  The predict is mhe_ekf_run's; at a step with
+ * 0 < nz <= pmax, with x_0 = mu-:
+ *   pass i:  (h, H) at x_i,  e = z - h - H (mu- - x_i),  P = H S- H^T + R = L L^T,
+ *            Y = L^-1 H S-,  w = L^-1 e,  x_{i+1} = mu- + Y^T w,
+ *            step = max_c |x_{i+1,c} - x_{i,c}|;  stop when !(step > tol) or i + 1 == max_iter
+ *   after:   mu = x_{i+1},  S = S- - Y^T Y with the Y of the last pass.
+ * With max_iter = 1 the step is mhe_ekf_run's general-R step, term by term.  Only the upper
+ * triangle of Q is read (an entry of S- below the diagonal is computed as its mirror image), so
+ * S_hist and S are bitwise symmetric.  One wavefront per filter for every R: dims->r_diag is
+ * ignored.  mhe_iekf_args holds mhe_ekf_args' fields in order, then:
+ *   tol       >= 0, an absolute max-norm in the state's own units; 0: every corrected step makes
+ *             max_iter passes (the step is not tested).  With tol > 0 a NaN step stops the
+ *             iteration.  Below the rounding floor of the
+ *             rows (about 1e-8 m for pseudoranges of 2e7 m) the counts depend on rounding.
+ *   n_iter    optional per-step output laid out as nis: the passes made; 0 on a predict-only
+ *             step (nz = 0, nz > pmax, or every row screened out).
+ *   max_iter  1..64
+ *   reserved0 must be 0
+ * gate (0: no screening) is mhe_ekf_args' marginal rule d2_i = e_i^2 / P_ii > gate, evaluated
+ * once, in pass 0, at the prediction; the kept rows stay fixed for the later passes.  nis,
+ * loglik and rej are pass 0's over the kept rows: the innovation likelihood at the prediction,
+ * as mhe_ekf_run_args reports it.  status: 1 if any pass met a pivot that is not positive and
+ * finite, 2 if nz > pmax at some step.  Refusals and return codes are mhe_ekf_run_args';
+ * in addition MHE_ERR_DIMS for max_iter outside 1..64, a NaN or negative tol, reserved0 != 0.
+ */
+typedef struct mhe_iekf_args {
+  int32_t struct_size; /* = sizeof(mhe_iekf_args) */
+  int32_t batch, steps;
+  double* mu;
+  double* S;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const double* Q;
+  const double* R;
+  int64_t r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int32_t* status;
+  double gate;
+  double* nis;
+  double* loglik;
+  int32_t* rej;
+  double tol;
+  int32_t* n_iter;
+  int32_t max_iter;
+  int32_t reserved0;
+} mhe_iekf_args;
+
+int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args, void* stream);
+
+/*
  * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
  * (added to ABI v11; no existing struct or function changed).  One filter per lane;
  * a filter's result does not depend on the batch or on its place in it.

@@ -158,9 +158,29 @@ def _gate_value(gate):
     return float(gate)
 
 
+MAX_ITERATIONS = 64
+
+
+def _iter_values(iterations, iter_tol, method="auto"):
+    """(max_iter, tol) of mhe_iekf_args for run_batch's `iterations` / `iter_tol`; iterations=None
+    -> (None, 0.0).  Anything but an int in 1..64 and a number >= 0 raises ValueError, and so
+    does method="lane" with iterations (no lane-per-filter form of the iterated filter exists)."""
+    if isinstance(iter_tol, (bool, np.bool_)) or not isinstance(iter_tol, (int, float, np.integer, np.floating)) \
+            or not float(iter_tol) >= 0.0:
+        raise ValueError(f"iter_tol must be a number >= 0, not {iter_tol!r}")
+    if iterations is None:
+        return None, float(iter_tol)
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) \
+            or not 1 <= int(iterations) <= MAX_ITERATIONS:
+        raise ValueError(f"iterations must be None or an int in 1..{MAX_ITERATIONS}, not {iterations!r}")
+    if method == "lane":
+        raise ValueError('iterations with method="lane": the iterated filter has the wave form only')
+    return int(iterations), float(iter_tol)
+
+
 def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=None, stream=None,
               keep_history=True, method="auto", inputs="batch_outer", dyn_params=None, gate=None,
-              innovations=False):
+              innovations=False, iterations=None, iter_tol=0.0):
     """Run B independent filters for T steps in one launch.
 
     mu0 (B,n), S0 (B,n,n), U (B,T,m), Z (B,T,pmax), nz (B,T) valid rows per step
@@ -193,9 +213,26 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     views of batch-innermost storage.  Without either keyword the call and its result
     are what they were (mhe_ekf_run's instances; otherwise mhe_ekf_run_args').
 
+    iterations: None, or an int in 1..64: the iterated EKF (mhe_iekf_run, one wavefront per
+    filter for every R; method="lane" is refused).  A step's correction becomes the
+    Gauss-Newton solve of its MAP problem: with x_0 = mu-,
+        pass i:  (h, H) at x_i,  e = z - h - H (mu- - x_i),  P = H S- H^T + R,
+                 K = S- H^T P^-1,  x_{i+1} = mu- + K e
+        stop when  not (max_c |x_{i+1,c} - x_{i,c}| > iter_tol)  or after `iterations` passes
+        then     mu = x_{i+1},  S = S- - K H S- with the last pass's H.
+    iterations=1 is the EKF step.  iter_tol is an absolute max-norm in the state's own units
+    (0: every corrected step makes `iterations` passes).  It must sit above the rounding floor
+    of the rows -- about 1e-8 m for pseudoranges of 2e7 m -- or the step stalls there and the
+    counts depend on rounding.  gate screens once, at the prediction (pass 0), and the kept rows
+    stay fixed; nis, loglik and rejected are pass 0's, the EKF's definition.  n_iter (B,T) int32,
+    the passes each step made (0: predict-only), is appended to the returned tuple last, after
+    the innovations triple when that is present.  smooth_batch takes an iterated run's history
+    as any other.  iterations=None is the call as it was.
+
     stream: a torch stream to order the work on (default: the current one); outputs
     belong to it (mhe.streams)."""
     gate = _gate_value(gate)
+    iterations, iter_tol = _iter_values(iterations, iter_tol, method)
     import torch
 
     from mhe.streams import launch_stream
@@ -208,11 +245,11 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with launch_stream(stream, dev) as (s, cur):
         return _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history,
-                          method, inputs, dp, gate, bool(innovations))
+                          method, inputs, dp, gate, bool(innovations), iterations, iter_tol)
 
 
 def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history, method,
-               inputs, dp, gate=0.0, innovations=False):
+               inputs, dp, gate=0.0, innovations=False, iterations=None, iter_tol=0.0):
     """run_batch on torch stream s (staging and allocation ordered on s)."""
     import torch
 
@@ -254,7 +291,11 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     mh_st = torch.empty((T, n, B), dtype=torch.float64, device=dev) if keep_history else None
     Sh_st = torch.empty((T, n, n, B), dtype=torch.float64, device=dev) if keep_history else None
     st = torch.empty(B, dtype=torch.int32, device=dev)
-    if method == "auto":
+    if iterations is not None:
+        if method not in ("auto", "wave"):
+            raise ValueError(f"unknown method {method!r}")
+        r_diag = False            # mhe_iekf_run ignores it: one wavefront per filter for every R
+    elif method == "auto":
         offd = Rt - torch.diag_embed(torch.diagonal(Rt, dim1=-2, dim2=-1))
         r_diag = Rt.numel() == 0 or not bool((offd != 0).any().item())
     elif method in ("lane", "wave"):
@@ -266,7 +307,20 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     for i in range(8):
         dims.dyn_par[i] = float(dp[i])
     lib = _lib.load()
-    if gate == 0.0 and not innovations:
+    if iterations is not None:
+        stats = tuple(torch.empty((T, B), dtype=dt_, device=dev)
+                      for dt_ in (torch.float64, torch.float64, torch.int32)) if innovations else ()
+        nis, ll, rej = stats if innovations else (None, None, None)
+        stats += (torch.empty((T, B), dtype=torch.int32, device=dev),)      # n_iter, last
+        args = _lib.MheIekfArgs(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
+                                Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
+                                PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
+                                r_bstride=r_b, r_sstride=r_s, mu_hist=_ptr(mh_st), S_hist=_ptr(Sh_st),
+                                status=st.data_ptr(), gate=gate, nis=_ptr(nis), loglik=_ptr(ll), rej=_ptr(rej),
+                                tol=iter_tol, n_iter=stats[-1].data_ptr(), max_iter=iterations)
+        rc = lib.mhe_iekf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_iekf_run")
+    elif gate == 0.0 and not innovations:
         rc = lib.mhe_ekf_run(ctypes.byref(dims), B, T, _ptr(mu), _ptr(S), _ptr(Ut), T * m, _ptr(Zt), T * pmax,
                              _ptr(nzt), T, _ptr(Pt), T * pmax * q, _ptr(Qt), _ptr(Rt), r_b, r_s, _ptr(mh_st),
                              _ptr(Sh_st), _ptr(st), ctypes.c_void_p(s.cuda_stream))
@@ -311,7 +365,8 @@ def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_par
     U (B,T,m) -- or (T,m,B) with inputs="batch_inner" -- and Q (n,n), dt, dyn_params: as
     given to run_batch.  mu0 (B,n), S0 (B,n,n): optionally the prior the filter started
     from; the smoothed prior is then returned too.  Measurements do not enter the backward
-    pass, so the history of a gated run (run_batch's ``gate``) smooths as any other.
+    pass, so the history of a gated run (run_batch's ``gate``) smooths as any other, and so
+    does that of an iterated run (run_batch's ``iterations``).
     Returns (mu_s (B,T,n), S_s (B,T,n,n), status (B)) and, with a prior, also
     (mu0_s (B,n), S0_s (B,n,n)).  status 1: a predicted covariance had no Cholesky factor or
     the history held a non-finite value; that filter is NaN from the failing step down.
@@ -379,14 +434,23 @@ class EKF(object):
         self.measurement = meas_func
         models(dyn_func, meas_func)  # fail at construction for unregistered plug-ins
 
-    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None, gate=None):
+    def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None, gate=None,
+               iterations=None, iter_tol=0.0):
         """One predict (+ correct when z is given) step, utils/ekf.py:20-38.
 
         gate (run_batch's; np.inf: statistics only): rows of z whose normalised innovation
         exceeds it are left out of the correction, and the object then holds ``nis``,
         ``loglik`` (floats) and ``rejected`` (bool, one per row of z) of this update.
-        Without a gate nothing changes."""
+        Without a gate nothing changes.
+
+        iterations, iter_tol (run_batch's): the iterated EKF -- the correction is repeated with
+        the measurement model relinearised at the iterate, x_{i+1} = mu- + K_i (z - h(x_i) -
+        H_i (mu- - x_i)), until the step's max-norm is not above iter_tol (absolute, in the
+        state's units; keep it above the rows' rounding floor, about 1e-8 m for pseudoranges)
+        or `iterations` passes are made; the object then holds ``n_iter`` (int), the passes
+        this update made (0: no correction)."""
         gv = _gate_value(gate)
+        iterations, iter_tol = _iter_values(iterations, iter_tol)
         meas = meas_func if meas_func is not None else self.measurement
         (_, n, m), (_, extra, q) = models(self.dynamics, meas)
         dt = float((dyn_func_params or {})["dt"])
@@ -409,6 +473,8 @@ class EKF(object):
             P[0, 0, :sp.shape[0]] = sp
             Rm = np.asarray(R, dtype=np.float64).reshape(1, pmax, pmax)
         kw = {} if gate is None else dict(gate=gv, innovations=True)
+        if iterations is not None:
+            kw.update(iterations=iterations, iter_tol=iter_tol)
         out = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
                         np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
                         dyn_params=dyn_func_params, **kw)
@@ -419,5 +485,7 @@ class EKF(object):
             self.nis, self.loglik = float(out[5][0, 0].item()), float(out[6][0, 0].item())
             word = int(out[7][0, 0].item()) & 0xFFFFFFFF
             self.rejected = np.array([bool((word >> i) & 1) for i in range(nz)], dtype=bool)
+        if iterations is not None:
+            self.n_iter = int(out[-1][0, 0].item())
         self.mu = mu[0].cpu().numpy()
         self.S = S[0].cpu().numpy()

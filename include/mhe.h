@@ -910,6 +910,101 @@ int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const
                    double* S0_s, int32_t* status, void* stream);
 
 /*
+ * The smoother above with the lag-one smoothed covariances as one more output (added within
+ * ABI v11; no existing struct or function changed).  mhe_ekf_lag_args holds mhe_ekf_smooth's
+ * arguments in order, then:
+ *   C  optional, laid out as S_s ((steps, n, n, B) with dims->hist_batch_inner, else
+ *      (B, steps, n, n)):  C_k = Cov(x_k, x_{k-1} | all data) = S_s[k] G_{k-1}^T  with
+ *      G_{k-1} = S_{k-1} F^T (S-)^-1 the smoother gain of step k-1 (k = -1: the prior).  All
+ *      n x n entries are written; C_k is not symmetric.  k = 1 .. steps-1, and k = 0 when the
+ *      smoothed prior is asked for (mu0_s or S0_s given); otherwise C_0 is written as NaN:
+ *      "not formed".  C must not overlap any input or any other output (MHE_ERR_DIMS); mu_s /
+ *      S_s may still alias the histories.  A filter that fails at step k (status 1) has C_j
+ *      NaN for j <= k + 1, next to its S_s[j] NaN for j <= k; no other filter is touched.
+ * C == NULL runs exactly what mhe_ekf_smooth runs.  mu_s, S_s, mu0_s, S0_s and status do not
+ * depend on C being asked for (bitwise).  Refusals precede any launch and are mhe_ekf_smooth's;
+ * a NULL or wrongly sized args struct is refused like dims.
+ */
+typedef struct mhe_ekf_lag_args {
+  int32_t struct_size; /* = sizeof(mhe_ekf_lag_args) */
+  int32_t batch, steps;
+  const double* mu_hist;
+  const double* S_hist;
+  const double* U;
+  int64_t u_bstride;
+  const double* Q;
+  const double* mu0;
+  const double* S0;
+  double* mu_s;
+  double* S_s;
+  double* mu0_s;
+  double* S0_s;
+  int32_t* status;
+  double* C;
+} mhe_ekf_lag_args;
+
+int mhe_ekf_smooth_args(const mhe_ekf_dims* dims, const mhe_ekf_lag_args* args, void* stream);
+
+/*
+ * EM sufficient statistics of the noise model from a smoothed history (added within ABI v11; no
+ * existing struct or function changed): what the M-step of the Shumway-Stoffer / extended-RTS EM
+ * update of Q and R needs, reduced per filter on the device.  One filter per lane; every sum runs
+ * in a fixed order (k increasing), so a filter's result is bitwise the same alone or in any batch.
+ * Dynamics, for k in K = {1 .. steps-1}, plus {0} when the smoothed prior is given:
+ *   (f, F) = f(mu_s[k-1], u_k)   value and Jacobian at the smoothed mean (k = 0: at mu0_s)
+ *   d = mu_s[k] - f
+ *   W_k = d d^T + S_s[k] - C_k F^T - F C_k^T + F S_s[k-1] F^T
+ *   Qsum = sum_K W_k  (upper triangle accumulated term by term and mirrored),  q_cnt = |K|
+ * Measurements, for every step with 0 < nz <= pmax and every row i < nz whose bit in rej is clear,
+ * with (h, H) at mu_s[k]:
+ *   r2[k][i] = (z_i - h_i)^2 + H_i S_s[k] H_i^T,   r_cnt = number of such rows
+ * and r2 = 0 for every other row i < pmax.  Only these diagonal second moments are formed.  The
+ * all-zero Jacobian row of MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS is kept as the filter has it.
+ * Of dims this call reads struct_size, n, m, pmax, q, dyn_model, meas_model, dt, dyn_par,
+ * hist_batch_inner (the layout of mu_s, S_s, C, rej and r2 alike) and in_batch_inner (U, Z, nz, PAR).
+ *   mu_s, S_s, C     what mhe_ekf_smooth_args wrote; of S_s the upper triangle is read
+ *   mu0_s (B,n), S0_s (B,n,n)   optional, together: the smoothed prior; C_0 is then read
+ *   U, Z, nz, PAR and their strides   as mhe_ekf_run
+ *   rej      optional, the mask mhe_ekf_run_args wrote ((steps, B) with hist_batch_inner, else
+ *            (B, steps)): bit i set = row i is not counted
+ *   Qsum (B,n,n), q_cnt (B), r_cnt (B)   batch outermost;  r2 (steps, pmax, B) with
+ *            hist_batch_inner, else (B, steps, pmax)
+ *   status (B, optional): 0 ok; 1 a non-finite value was met in what the sums read: that
+ *            filter's Qsum and r2 are NaN, no other filter is touched; 2 nz > pmax at some step
+ *            (its rows are skipped, as in the filters).  1 wins over 2.
+ * Stream-ordered: no host synchronisation, no allocation.  Refusals precede any launch:
+ * MHE_ERR_NULL for a missing struct or required pointer (mu0_s without S0_s or the reverse),
+ * MHE_ERR_DIMS for a wrong struct_size, negative batch / steps, pmax outside 1..32, q != 3, the
+ * vehicle's M / I_Z unset, MHE_ERR_MODEL for a pair that is not compiled (batch == 0 or
+ * steps == 0: MHE_OK, nothing is read).
+ */
+typedef struct mhe_em_args {
+  int32_t struct_size; /* = sizeof(mhe_em_args) */
+  int32_t batch, steps;
+  const double* mu_s;
+  const double* S_s;
+  const double* C;
+  const double* mu0_s;
+  const double* S0_s;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const int32_t* rej;
+  double* Qsum;
+  int32_t* q_cnt;
+  double* r2;
+  int32_t* r_cnt;
+  int32_t* status;
+} mhe_em_args;
+
+int mhe_ekf_em_stats(const mhe_ekf_dims* dims, const mhe_em_args* args, void* stream);
+
+/*
  * Unscented fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ukf_run wrote
  * (added within ABI v11; no existing struct or function changed).  One wavefront per filter, by
  * the dynamics' VALUES only: no Jacobian enters.  c, wm and wc are mhe_ukf_run's, from the same

@@ -532,6 +532,16 @@ struct RtsArgs {
   int* status;
 };
 
+// the LAG instances (k_ekf_rts<.., true>) take the lag-one output as well; the others keep the
+// kernel arguments they had
+struct RtsLagArgs : RtsArgs {
+  double* C;  // C_k = Cov(x_k, x_{k-1} | all data) = Ss_k M_{k-1}, all n x n entries, laid out as S_s; no aliasing
+};
+template <bool LAG>
+struct RtsK { using type = RtsArgs; };
+template <>
+struct RtsK<true> { using type = RtsLagArgs; };
+
 // where step k's w-entry record of filter b starts and the stride between its entries;
 // k = -1 is the prior's (B, w) array
 struct RtsRec {
@@ -600,8 +610,16 @@ __device__ __forceinline__ bool rts_finite(const double* xs, const double* Ss) {
   return t < INFINITY;
 }
 
-template <class DYN>
-__global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a) {
+// LAG: the lag-one smoothed covariance C_{k+1} = Ss_{k+1} M as one more output of step k.  With
+// D = Ss_{k+1} - S- the final sum already forms e = D M(:, c) per column, and S- M is the
+// pre-solve A = G S_k, so C_{k+1}(:, c) = e + A(:, c): no second product with Ss_{k+1}.  M has
+// overwritten A by then; column c of A is formed again from G (kept live: its structural
+// non-zeros only) and column c of S_k, which the accumulation on S_k's triangle has not yet
+// touched when column c is reached (it writes (r, c'), r <= c' < c, before).  C_0 needs the
+// prior; without one it is written as NaN.  A failing step k leaves C NaN from k+1 down.
+// LAG = false is the code as it was.
+template <class DYN, bool LAG = false>
+__global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(typename RtsK<LAG>::type a) {
   constexpr int n = DYN::n;
   using LS = LaneS<n>;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -633,8 +651,10 @@ __global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a)
     RtsIn<DYN> nx;
     rts_load<DYN>(a, b, max(k - 1, kmin), nx);
     double xp[n], A[n * n], L[LS::size];
+    double Gk[LAG ? n * n : 1];  // LAG: G outlives the block below
     {
-      double G[n * n];
+      double Gb[LAG ? 1 : n * n];
+      double* G = LAG ? Gk : Gb;
       DYN::step(in.mu, in.u, a.dt, a.dp, xp, G);
 #pragma unroll
       for (int c = 0; c < n; ++c) {  // row c of A = G S_k, then column c of S- = A G^T + Q
@@ -711,6 +731,17 @@ __global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a)
         for (int j = 0; j < n; ++j) s += Ss[LS::at(l, j)] * A[j * n + c];
         e[l] = s;
       }
+      if constexpr (LAG) {
+        const RtsRec rc = rts_rec(a, b, k + 1, n * n);
+#pragma unroll
+        for (int r = 0; r < n; ++r) {
+          double s = 0.0;  // A(r, c) = (G S_k)(r, c), S_k's column c still as loaded
+#pragma unroll
+          for (int kk = 0; kk < n; ++kk)
+            if (DYN::gnz(r, kk)) s += Gk[r * n + kk] * in.S[LS::at(kk, c)];
+          a.C[rc.off + (r * n + c) * rc.es] = bad ? NAN : e[r] + s;
+        }
+      }
 #pragma unroll
       for (int r = 0; r <= c; ++r) {
         double s = 0.0;
@@ -722,6 +753,13 @@ __global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a)
 #pragma unroll
     for (int i = 0; i < LS::size; ++i) Ss[i] = in.S[i];
     if (bad || !rts_finite<n>(xs, Ss)) {
+      if constexpr (LAG) {
+        if (!bad) {  // met only now: the record written above goes with the step
+          const RtsRec rc = rts_rec(a, b, k + 1, n * n);
+#pragma unroll
+          for (int i = 0; i < n * n; ++i) a.C[rc.off + i * rc.es] = NAN;
+        }
+      }
       bad = true;
 #pragma unroll
       for (int c = 0; c < n; ++c) xs[c] = NAN;
@@ -731,27 +769,41 @@ __global__ __launch_bounds__(256, DYN::n <= 5 ? 2 : 1) void k_ekf_rts(RtsArgs a)
     rts_store<n>(a, b, k, xs, Ss);
     in = nx;
   }
+  if constexpr (LAG) {
+    if (kmin == 0) {  // no prior: C_0 is not formed
+      const RtsRec rc = rts_rec(a, b, 0, n * n);
+#pragma unroll
+      for (int i = 0; i < n * n; ++i) a.C[rc.off + i * rc.es] = NAN;
+    }
+  }
   if (a.status) a.status[b] = bad ? 1 : 0;
 }
 
 template <class DYN>
-int launch_rts(const RtsArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((k_ekf_rts<DYN>), dim3((a.batch + 255) / 256), dim3(256), 0, st, a);
+int launch_rts(const RtsLagArgs& g, hipStream_t st) {
+  if (g.C) {
+    hipLaunchKernelGGL((k_ekf_rts<DYN, true>), dim3((g.batch + 255) / 256), dim3(256), 0, st, g);
+  } else {
+    const RtsArgs& a = g;
+    hipLaunchKernelGGL((k_ekf_rts<DYN>), dim3((a.batch + 255) / 256), dim3(256), 0, st, a);
+  }
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
-}  // namespace mhe_ekf
+// [p, p + np) and [q, q + nq) doubles share a byte
+inline bool overlaps(const double* p, size_t np, const double* q, size_t nq) {
+  return p && q && p < q + nq && q < p + np;
+}
 
-extern "C" int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const double* mu_hist,
-                              const double* S_hist, const double* U, int64_t u_bstride, const double* Q,
-                              const double* mu0, const double* S0, double* mu_s, double* S_s, double* mu0_s,
-                              double* S0_s, int32_t* status, void* stream) {
-  using namespace mhe_ekf;
+// mhe_ekf_smooth (C = nullptr) and mhe_ekf_smooth_args
+int smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const double* mu_hist, const double* S_hist,
+           const double* U, int64_t u_bstride, const double* Q, const double* mu0, const double* S0, double* mu_s,
+           double* S_s, double* mu0_s, double* S0_s, int32_t* status, double* C, void* stream) {
   if (!dims) return MHE_ERR_NULL;
   if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
   if (batch < 0 || steps < 0) return MHE_ERR_DIMS;
   if (batch == 0 || steps == 0) return MHE_OK;
-  int (*run)(const RtsArgs&, hipStream_t) = nullptr;
+  int (*run)(const RtsLagArgs&, hipStream_t) = nullptr;
   if (dims->dyn_model == MHE_EKF_DYN_GNSS_POS_AND_BIAS) {
     if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
     run = launch_rts<EkfGnssPosAndBias>;
@@ -764,17 +816,47 @@ extern "C" int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t s
   }
   if (!mu_hist || !S_hist || !U || !Q || !mu_s || !S_s) return MHE_ERR_NULL;
   if ((mu0_s || S0_s) && (!mu0 || !S0)) return MHE_ERR_NULL;
-  RtsArgs a = {};
+  if (C) {  // C is written while the inputs and the other outputs are still being read and written
+    const size_t n = (size_t)dims->n, bt = (size_t)batch * (size_t)steps, nc = bt * n * n;
+    const size_t nu = dims->in_batch_inner ? bt * (size_t)dims->m
+                                           : (size_t)(batch - 1) * (size_t)u_bstride + (size_t)steps * (size_t)dims->m;
+    if (overlaps(C, nc, mu_hist, bt * n) || overlaps(C, nc, S_hist, nc) || overlaps(C, nc, U, nu) ||
+        overlaps(C, nc, Q, n * n) || overlaps(C, nc, mu0, batch * n) || overlaps(C, nc, S0, batch * n * n) ||
+        overlaps(C, nc, mu_s, bt * n) || overlaps(C, nc, S_s, nc) || overlaps(C, nc, mu0_s, batch * n) ||
+        overlaps(C, nc, S0_s, batch * n * n))
+      return MHE_ERR_DIMS;
+  }
+  RtsLagArgs a = {};
   a.batch = batch; a.steps = steps; a.dt = dims->dt;
   for (int i = 0; i < 8; ++i) a.dp[i] = dims->dyn_par[i];
   a.mu_hist = mu_hist; a.S_hist = S_hist; a.U = U; a.u_bstride = u_bstride; a.es = 1; a.Q = Q;
   a.mu0 = mu0; a.S0 = S0; a.mu_s = mu_s; a.S_s = S_s; a.mu0_s = mu0_s; a.S0_s = S0_s; a.status = status;
+  a.C = C;
   a.hist_bi = dims->hist_batch_inner != 0;
   if (dims->in_batch_inner) {  // U (steps, m, B)
     a.es = batch;
     a.u_bstride = 1;
   }
   return run(a, (hipStream_t)stream);
+}
+
+}  // namespace mhe_ekf
+
+extern "C" int mhe_ekf_smooth(const mhe_ekf_dims* dims, int32_t batch, int32_t steps, const double* mu_hist,
+                              const double* S_hist, const double* U, int64_t u_bstride, const double* Q,
+                              const double* mu0, const double* S0, double* mu_s, double* S_s, double* mu0_s,
+                              double* S0_s, int32_t* status, void* stream) {
+  return mhe_ekf::smooth(dims, batch, steps, mu_hist, S_hist, U, u_bstride, Q, mu0, S0, mu_s, S_s, mu0_s, S0_s,
+                         status, nullptr, stream);
+}
+
+extern "C" int mhe_ekf_smooth_args(const mhe_ekf_dims* dims, const mhe_ekf_lag_args* args, void* stream) {
+  if (!dims || !args) return MHE_ERR_NULL;
+  if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
+  if (args->struct_size != (int32_t)sizeof(mhe_ekf_lag_args)) return MHE_ERR_DIMS;
+  return mhe_ekf::smooth(dims, args->batch, args->steps, args->mu_hist, args->S_hist, args->U, args->u_bstride,
+                         args->Q, args->mu0, args->S0, args->mu_s, args->S_s, args->mu0_s, args->S0_s, args->status,
+                         args->C, stream);
 }
 
 extern "C" int mhe_ekf_run_args(const mhe_ekf_dims* dims, const mhe_ekf_args* args, void* stream) {

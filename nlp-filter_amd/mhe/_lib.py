@@ -81,6 +81,19 @@ class MheUkfSmoothArgs(_Sized):
                 ("beta", c_dbl), ("kappa", c_dbl)]
 
 
+class MheEkfLagArgs(_Sized):
+    _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu_hist", c_vp), ("S_hist", c_vp),
+                ("U", c_vp), ("u_bstride", c_i64), ("Q", c_vp), ("mu0", c_vp), ("S0", c_vp), ("mu_s", c_vp),
+                ("S_s", c_vp), ("mu0_s", c_vp), ("S0_s", c_vp), ("status", c_vp), ("C", c_vp)]
+
+
+class MheEmArgs(_Sized):
+    _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu_s", c_vp), ("S_s", c_vp),
+                ("C", c_vp), ("mu0_s", c_vp), ("S0_s", c_vp), ("U", c_vp), ("u_bstride", c_i64), ("Z", c_vp),
+                ("z_bstride", c_i64), ("nz", c_vp), ("nz_bstride", c_i64), ("PAR", c_vp), ("par_bstride", c_i64),
+                ("rej", c_vp), ("Qsum", c_vp), ("q_cnt", c_vp), ("r2", c_vp), ("r_cnt", c_vp), ("status", c_vp)]
+
+
 class MheLsDims(_Sized):
     _fields_ = [("struct_size", c_i32), ("slots", c_i32), ("max_iter", c_i32), ("warm", c_i32), ("with_vel", c_i32), ("tol", c_dbl)]
 
@@ -148,6 +161,8 @@ SIGNATURES = {
     "mhe_ukf_run_gated": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfGateArgs), c_vp]),
     "mhe_ekf_smooth": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp]),
+    "mhe_ekf_smooth_args": (ctypes.c_int, [_PE, ctypes.POINTER(MheEkfLagArgs), c_vp]),
+    "mhe_ekf_em_stats": (ctypes.c_int, [_PE, ctypes.POINTER(MheEmArgs), c_vp]),
     "mhe_ukf_smooth": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfSmoothArgs), c_vp]),
     "mhe_ls_run": (ctypes.c_int, [_PL, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp]),

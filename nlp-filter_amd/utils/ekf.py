@@ -355,8 +355,15 @@ def _hist_storage(t, w):
     return t.contiguous(), False
 
 
+def _flag(name, v):
+    """A keyword that is True or False and nothing else (ValueError otherwise)."""
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False, not {v!r}")
+    return bool(v)
+
+
 def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_params=None, inputs="batch_outer",
-                 device=None, stream=None):
+                 device=None, stream=None, lag_one=False):
     """Fixed-interval (Rauch-Tung-Striebel) smoother over a filtered history, B filters
     in one launch of ``mhe_ekf_smooth`` (one filter per lane).
 
@@ -371,7 +378,16 @@ def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_par
     (mu0_s (B,n), S0_s (B,n,n)).  status 1: a predicted covariance had no Cholesky factor or
     the history held a non-finite value; that filter is NaN from the failing step down.
 
+    lag_one=True (``mhe_ekf_smooth_args``) appends C (B,T,n,n) last to the returned tuple, the
+    lag-one smoothed covariances C[:, k] = Cov(x_k, x_{k-1} | all data) = S_s[k] G_{k-1}^T with
+    G_{k-1} the smoother gain of step k-1: all n x n entries, not symmetric, a view of
+    batch-innermost storage when the histories were.  C[:, 0] pairs step 0 with the prior: it is
+    formed when mu0 / S0 are given and NaN otherwise.  A filter with status 1 has C NaN from the
+    step above the failing one down.  Everything else returned is bitwise what it is without the
+    keyword, and lag_one=False is the call as it was.
+
     stream: as run_batch (mhe.streams)."""
+    lag_one = _flag("lag_one", lag_one)
     import torch
 
     from mhe.streams import keep_alive, launch_stream
@@ -414,14 +430,210 @@ def smooth_batch(dyn_func, mu_hist, S_hist, U, Q, dt, mu0=None, S0=None, dyn_par
         for i in range(8):
             dims.dyn_par[i] = float(dp[i])
         lib = _lib.load()
-        rc = lib.mhe_ekf_smooth(ctypes.byref(dims), B, T, _ptr(mh), _ptr(Sh), _ptr(Ut), T * m, _ptr(Qt), _ptr(m0),
-                                _ptr(S0t), _ptr(ms), _ptr(Ss), _ptr(m0s), _ptr(S0s), _ptr(st),
-                                ctypes.c_void_p(s.cuda_stream))
-        _lib.check(rc, "mhe_ekf_smooth")
-        keep_alive(s, cur, mh, Sh, Ut, Qt, m0, S0t, ms, Ss, m0s, S0s, st)
+        Ct = torch.empty_like(Sh) if lag_one else None
+        if lag_one:
+            args = _lib.MheEkfLagArgs(batch=B, steps=T, mu_hist=mh.data_ptr(), S_hist=Sh.data_ptr(), U=Ut.data_ptr(),
+                                      u_bstride=T * m, Q=Qt.data_ptr(), mu0=_ptr(m0), S0=_ptr(S0t),
+                                      mu_s=ms.data_ptr(), S_s=Ss.data_ptr(), mu0_s=_ptr(m0s), S0_s=_ptr(S0s),
+                                      status=st.data_ptr(), C=Ct.data_ptr())
+            rc = lib.mhe_ekf_smooth_args(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+            _lib.check(rc, "mhe_ekf_smooth_args")
+        else:
+            rc = lib.mhe_ekf_smooth(ctypes.byref(dims), B, T, _ptr(mh), _ptr(Sh), _ptr(Ut), T * m, _ptr(Qt), _ptr(m0),
+                                    _ptr(S0t), _ptr(ms), _ptr(Ss), _ptr(m0s), _ptr(S0s), _ptr(st),
+                                    ctypes.c_void_p(s.cuda_stream))
+            _lib.check(rc, "mhe_ekf_smooth")
+        keep_alive(s, cur, mh, Sh, Ut, Qt, m0, S0t, ms, Ss, m0s, S0s, st, Ct)
         if mh_bi:
             ms, Ss = ms.permute(2, 0, 1), Ss.permute(3, 0, 1, 2)
-        return (ms, Ss, st, m0s, S0s) if prior else (ms, Ss, st)
+            Ct = Ct.permute(3, 0, 1, 2) if lag_one else None
+        out = (ms, Ss, st, m0s, S0s) if prior else (ms, Ss, st)
+        return out + (Ct,) if lag_one else out
+
+
+def em_stats(dyn_func, meas_func, mu_s, S_s, C, U, Z, nz, dt, sat_pos, mu0_s=None, S0_s=None, rejected=None,
+             dyn_params=None, inputs="batch_outer", device=None, stream=None):
+    """EM sufficient statistics of the noise model from a smoothed history, B filters in one
+    launch of ``mhe_ekf_em_stats`` (one filter per lane).
+
+    mu_s (B,T,n), S_s (B,T,n,n), C (B,T,n,n): what smooth_batch(..., lag_one=True) returned (its
+    batch-innermost views go to the kernel without a copy); mu0_s (B,n), S0_s (B,n,n):
+    optionally the smoothed prior, and step 0 then counts in the dynamics' sum.  U, Z, nz,
+    sat_pos, dt, dyn_params, inputs: as given to run_batch.  rejected (B,T) int32: optionally
+    the mask a gated run_batch returned; bit i set leaves row i of that step out.
+    Per filter, with (f, F) the dynamics and its Jacobian at the smoothed mean of step k-1 and
+    (h, H) the measurement model at that of step k:
+        W_k = d d^T + S_s[k] - C_k F^T - F C_k^T + F S_s[k-1] F^T,   d = mu_s[k] - f
+        Qsum = sum of W_k over k = 1..T-1 (and 0 with the smoothed prior),  q_cnt their number
+        r2[k, i] = (z_i - h_i)^2 + H_i S_s[k] H_i^T for every counted row (i < nz_k <= pmax, not
+        rejected), 0 for every other row;  r_cnt the number of counted rows.
+    Returns (Qsum (B,n,n) bitwise symmetric, q_cnt (B) int32, r2 (B,T,pmax), r_cnt (B) int32,
+    status (B) int32) on the device.  status 1: a non-finite value was met, that filter's Qsum
+    and r2 are NaN; 2: nz > pmax at some step (that step's rows are skipped).  The M-step is
+    the caller's: Q = sum_b Qsum / sum_b q_cnt, and r2 pooled as the application needs (per
+    satellite, per elevation, one scale: fit_noise does the last).
+
+    stream: as run_batch (mhe.streams)."""
+    (did, n, m), (mid, _, q) = models(dyn_func, meas_func)
+    if dyn_params is not None and "dt" in dyn_params:
+        dt = dyn_params["dt"]
+    if inputs not in ("batch_outer", "batch_inner"):
+        raise ValueError(f"unknown inputs layout {inputs!r}")
+    if (mu0_s is None) != (S0_s is None):
+        raise ValueError("em_stats: mu0_s and S0_s go together")
+    bi = inputs == "batch_inner"
+    shp = lambda a: tuple(np.shape(a)) if not hasattr(a, "shape") else tuple(a.shape)   # noqa: E731
+    if len(shp(mu_s)) != 3 or len(shp(Z)) != 3:
+        raise ValueError("em_stats: mu_s must be (B,T,n) and Z (B,T,pmax) or (T,pmax,B)")
+    B, T = shp(mu_s)[:2]
+    pmax = shp(Z)[1] if bi else shp(Z)[2]
+    if not 1 <= pmax <= MAXP:
+        raise ValueError(f"between 1 and {MAXP} measurement rows per step")
+    want = ((T, m, B), (T, pmax, B), (T, B), (T, pmax, q, B)) if bi else \
+        ((B, T, m), (B, T, pmax), (B, T), (B, T, pmax, q))
+    if shp(mu_s) != (B, T, n) or shp(S_s) != (B, T, n, n) or shp(C) != (B, T, n, n) \
+            or (shp(U), shp(Z), shp(nz), shp(sat_pos)) != want \
+            or (mu0_s is not None and (shp(mu0_s) != (B, n) or shp(S0_s) != (B, n, n))) \
+            or (rejected is not None and shp(rejected) != (B, T)):
+        raise ValueError("em_stats: inconsistent shapes")
+    verify(dyn_func, meas_func, dict(dyn_params or {}, dt=dt))
+    dp = dyn_par(dyn_func, dyn_params)
+    import torch
+
+    from mhe.streams import keep_alive, launch_stream
+
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with launch_stream(stream, dev) as (s, cur):
+        def d(a, dt_=torch.float64):
+            return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=dt_, device=dev)
+
+        ms, ms_bi = _hist_storage(d(mu_s), (n,))
+        Ss, Ss_bi = _hist_storage(d(S_s), (n, n))
+        Ct, C_bi = _hist_storage(d(C), (n, n))
+        hbi = ms_bi and Ss_bi and C_bi          # one layout flag covers the three histories, the mask and r2
+        if not hbi:
+            ms, Ss, Ct = d(mu_s).contiguous(), d(S_s).contiguous(), d(C).contiguous()
+        rj = None
+        if rejected is not None:
+            rj = d(rejected, torch.int32)
+            rj = rj.permute(1, 0).contiguous() if hbi else rj.contiguous()
+        Ut, Zt, nzt, Pt = d(U).contiguous(), d(Z).contiguous(), d(nz, torch.int32).contiguous(), \
+            d(sat_pos).contiguous()
+        prior = mu0_s is not None
+        m0, S0t = (d(mu0_s).contiguous(), d(S0_s).contiguous()) if prior else (None, None)
+        Qsum = torch.empty((B, n, n), dtype=torch.float64, device=dev)
+        r2 = torch.empty((T, pmax, B) if hbi else (B, T, pmax), dtype=torch.float64, device=dev)
+        q_cnt, r_cnt, st = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+        dims = _lib.MheEkfDims(n=n, m=m, pmax=pmax, q=q, dyn_model=did, meas_model=mid, dt=float(dt),
+                               hist_batch_inner=int(hbi), in_batch_inner=int(bi))
+        for i in range(8):
+            dims.dyn_par[i] = float(dp[i])
+        args = _lib.MheEmArgs(batch=B, steps=T, mu_s=ms.data_ptr(), S_s=Ss.data_ptr(), C=Ct.data_ptr(),
+                              mu0_s=_ptr(m0), S0_s=_ptr(S0t), U=Ut.data_ptr(), u_bstride=T * m, Z=Zt.data_ptr(),
+                              z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T, PAR=Pt.data_ptr(),
+                              par_bstride=T * pmax * q, rej=_ptr(rj), Qsum=Qsum.data_ptr(), q_cnt=q_cnt.data_ptr(),
+                              r2=r2.data_ptr(), r_cnt=r_cnt.data_ptr(), status=st.data_ptr())
+        rc = _lib.load().mhe_ekf_em_stats(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+        _lib.check(rc, "mhe_ekf_em_stats")
+        keep_alive(s, cur, ms, Ss, Ct, rj, Ut, Zt, nzt, Pt, m0, S0t, Qsum, r2, q_cnt, r_cnt, st)
+        return Qsum, q_cnt, (r2.permute(2, 0, 1) if hbi else r2), r_cnt, st
+
+
+Q_STRUCTURES = ("full", "diag")
+MAX_ROUNDS = 1000
+
+
+def _fit_values(rounds, fit_Q, fit_R, q_structure):
+    """fit_noise's keywords, validated as _gate_value / _iter_values validate theirs."""
+    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) \
+            or not 1 <= int(rounds) <= MAX_ROUNDS:
+        raise ValueError(f"rounds must be an int in 1..{MAX_ROUNDS}, not {rounds!r}")
+    if q_structure not in Q_STRUCTURES:
+        raise ValueError(f"q_structure must be one of {Q_STRUCTURES}, not {q_structure!r}")
+    return int(rounds), _flag("fit_Q", fit_Q), _flag("fit_R", fit_R), q_structure
+
+
+def fit_noise(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, rounds=10, fit_Q=True, fit_R=True,
+              q_structure="full", gate=None, dyn_params=None, inputs="batch_outer", device=None, stream=None):
+    """EM identification of the EKF's noise model (Shumway-Stoffer; Sarkka, Bayesian Filtering
+    and Smoothing, ch. 12, the extended-RTS form) over a batch of logs that share Q and R.
+
+    mu0 .. sat_pos, gate, dyn_params, inputs: as run_batch's; Q (n,n) and R ((T,pmax,pmax) or
+    (B,T,pmax,pmax)) are the starting guess.  Each of `rounds` rounds runs
+    run_batch(innovations=True, gate=gate), smooth_batch with the prior and lag_one=True,
+    em_stats (with the run's rejection mask when gated) and then the M-step as torch
+    reductions on the device, pooled over the filters whose three statuses are all 0:
+        Q <- sum_b Qsum_b / sum_b q_cnt_b                      (q_structure="diag": its diagonal only)
+        rho_round = sum r2[b,k,i] / R[k,i,i] / sum_b r_cnt_b;   R <- rho_round R
+    so R keeps its given shape and structure and is fitted by ONE common scale (fit_R needs a
+    diagonal R: ValueError otherwise); Q is one matrix shared by the batch.  The linearisations
+    are the filter's and the smoother's own (the EKF's prediction and the smoothed means), so
+    this is the extended-RTS approximation of EM: the likelihood usually rises at every round
+    but is not guaranteed to -- read `loglik`.  No history leaves the device.
+    Returns a dict of device tensors and ints: Q (n,n), R (as given), rho (the cumulative scale
+    on the given R), loglik (rounds,) the summed log-likelihood (over the used filters) of the
+    parameters that ENTERED each round, n_used (the filters pooled in the last round),
+    n_iter = rounds."""
+    gate_v = _gate_value(gate)
+    rounds, fit_Q, fit_R, q_structure = _fit_values(rounds, fit_Q, fit_R, q_structure)
+    (_, n, m), (_, _, q) = models(dyn_func, meas_func)
+    if inputs not in ("batch_outer", "batch_inner"):
+        raise ValueError(f"unknown inputs layout {inputs!r}")
+    bi = inputs == "batch_inner"
+    shp = lambda a: tuple(np.shape(a)) if not hasattr(a, "shape") else tuple(a.shape)   # noqa: E731
+    if len(shp(mu0)) != 2 or len(shp(Z)) != 3:
+        raise ValueError("fit_noise: mu0 must be (B,n) and Z (B,T,pmax) or (T,pmax,B)")
+    B = shp(mu0)[0]
+    T, pmax = shp(Z)[:2] if bi else shp(Z)[1:]
+    if not 1 <= pmax <= MAXP:
+        raise ValueError(f"between 1 and {MAXP} measurement rows per step")
+    want = ((T, m, B), (T, pmax, B), (T, B), (T, pmax, q, B)) if bi else \
+        ((B, T, m), (B, T, pmax), (B, T), (B, T, pmax, q))
+    if shp(mu0) != (B, n) or shp(S0) != (B, n, n) or shp(Q) != (n, n) \
+            or (shp(U), shp(Z), shp(nz), shp(sat_pos)) != want \
+            or shp(R) not in ((T, pmax, pmax), (B, T, pmax, pmax)):
+        raise ValueError("fit_noise: inconsistent shapes")
+    if dyn_params is not None and "dt" in dyn_params:
+        dt = dyn_params["dt"]
+    verify(dyn_func, meas_func, dict(dyn_params or {}, dt=dt))
+    import torch
+
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    Qt = torch.as_tensor(np.asarray(Q) if not torch.is_tensor(Q) else Q, dtype=torch.float64, device=dev).clone()
+    Rt = torch.as_tensor(np.asarray(R) if not torch.is_tensor(R) else R, dtype=torch.float64, device=dev).clone()
+    offd = Rt - torch.diag_embed(torch.diagonal(Rt, dim1=-2, dim2=-1))     # method="auto"'s check, made once
+    r_diag = Rt.numel() == 0 or not bool((offd != 0).any().item())
+    if fit_R and not r_diag:
+        raise ValueError("fit_R needs a diagonal R (one common scale on the given R is fitted)")
+    method = "lane" if r_diag else "wave"
+    on_dev = [torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, device=dev)
+              for a in (mu0, S0, U, Z, nz, sat_pos)]
+    mu0, S0, U, Z, nz, sat_pos = on_dev
+    rho = torch.ones((), dtype=torch.float64, device=dev)
+    loglik = torch.zeros(rounds, dtype=torch.float64, device=dev)
+    n_used = torch.zeros((), dtype=torch.int64, device=dev)
+    kw = dict(dyn_params=dyn_params, inputs=inputs, device=dev, stream=stream)
+    for it in range(rounds):
+        mh, Sh, _, _, st_f, _, ll, rej = run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Qt, Rt, dt, sat_pos,
+                                                   method=method, gate=gate, innovations=True, **kw)
+        ms, Ss, st_s, m0s, S0s, C = smooth_batch(dyn_func, mh, Sh, U, Qt, dt, mu0=mu0, S0=S0, lag_one=True, **kw)
+        Qsum, q_cnt, r2, r_cnt, st_e = em_stats(dyn_func, meas_func, ms, Ss, C, U, Z, nz, dt, sat_pos, mu0_s=m0s,
+                                                S0_s=S0s, rejected=rej if gate_v != 0.0 else None, **kw)
+        ok = (st_f == 0) & (st_s == 0) & (st_e == 0)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        loglik[it] = torch.where(ok, ll.sum(1), zero).sum()
+        n_used = ok.sum()
+        if fit_Q:
+            Qn = torch.where(ok[:, None, None], Qsum, torch.zeros_like(Qsum)).sum(0) / (q_cnt * ok).sum()
+            Qt = torch.diag(torch.diagonal(Qn)) if q_structure == "diag" else Qn
+        if fit_R:
+            Rd = torch.diagonal(Rt, dim1=-2, dim2=-1)                       # (T,pmax) or (B,T,pmax)
+            ratio = torch.where(r2 > 0.0, r2 / Rd, torch.zeros_like(r2))    # uncounted rows are exactly 0
+            cnt = (r_cnt * ok).sum()
+            rr = torch.where(cnt > 0, torch.where(ok, ratio.sum((1, 2)), zero).sum() / cnt, torch.ones_like(rho))
+            Rt = Rt * rr
+            rho = rho * rr
+    return {"Q": Qt, "R": Rt, "rho": rho, "loglik": loglik, "n_used": n_used, "n_iter": rounds}
 
 
 class EKF(object):

@@ -13,7 +13,7 @@ cp $ROOT/nlp-filter_amd/csrc/*.h $ROOT/nlp-filter_amd/csrc/*.hip $S/csrc/
 cp $ROOT/include/mhe.h $S/include/
 for f in $FILES; do git -C $ROOT show $REV:$f > $S/$( [[ $f == include/* ]] && echo include || echo csrc )/$(basename $f); done
 FLAGS="-O3 --offload-arch=gfx950 -std=c++17 -fPIC -I$S/include -I$S/csrc $VFLAGS"
-for s in mhe_gn pair_vdp pair_integrators pair_gnss pair_vehicles pair_autocar pair_receivers mhe_ekf mhe_iekf mhe_ukf mhe_ls; do
+for s in mhe_gn pair_vdp pair_integrators pair_gnss pair_vehicles pair_autocar pair_receivers mhe_ekf mhe_iekf mhe_ukf mhe_ls mhe_em; do
   /opt/rocm/bin/hipcc $FLAGS -c -o $S/$s.o $S/csrc/$s.hip &
 done
 wait

@@ -880,6 +880,74 @@ typedef struct mhe_iekf_args {
 int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args, void* stream);
 
 /*
+ * Pseudo-Huber measurement rows for the iterated filter (added within v11; no existing struct or
+ * function changed): the M-estimate of each step's MAP problem by iteratively reweighted
+ * Gauss-Newton, the Huber-type Kalman correction.  The predict, the stop rule, tol, max_iter and
+ * the gate's meaning are mhe_iekf_run's.  At a step with 0 < nz <= pmax, with x_0 = mu-:
+ *   pass i:  (h, H) at x_i,  r_j = z_j - h_j,  t_j = r_j / delta_j,  s_j = sqrt(1 + t_j^2),
+ *            g_j = sqrt(s_j),  e = r - H (mu- - x_i),
+ *            P = H S- H^T + R~ = L L^T  with  R~_jl = R_jl * (g_j * g_l),
+ *            Y = L^-1 H S-,  w = L^-1 e,  x_{i+1} = mu- + Y^T w,  the same stop rule
+ *   after:   mu = x_{i+1},  S = S- - Y^T Y with the Y of the last pass,
+ *            omega_j = 1 / s_j of the last pass.
+ * For a diagonal R this is IRLS on the cost sum_j 2 (delta_j^2 / R_jj) (s_j - 1) + the prior's
+ * term: a row counts fully while |r_j| << delta_j and like |r_j| beyond it; delta is in the
+ * measurement's own units, as mhe_solve_args.meas_delta.  For any symmetric positive definite R
+ * it is the covariance inflation D^-1/2 R D^-1/2, D = diag omega; no R is refused.
+ * delta = +inf gives s = g = 1 exactly: the run is then bitwise mhe_iekf_run's.
+ * mhe_iekf_robust_args holds mhe_iekf_args' fields in order, then:
+ *   delta    every row's delta when DELTA is NULL: > 0, +inf allowed.  With DELTA given it must be 0.
+ *   DELTA    optional: one entry per row, laid out and strided exactly as Z (z_bstride,
+ *            dims->in_batch_inner).  Entries are not validated on the device: a zero or NaN entry
+ *            of a counted row gives a non-finite pivot, status 1 for that filter alone.
+ *   weights  optional output: omega of the last pass per row, pmax entries per step, laid out as
+ *            the per-step outputs ((steps, pmax, B) with dims->hist_batch_inner, else
+ *            (B, steps, pmax)); 0 for every row that was not applied (beyond nz, screened out, or
+ *            on a predict-only step).
+ * gate (0: no screening) is evaluated once, in pass 0, on the UNWEIGHTED diagonal
+ * pd_j = (H S- H^T)_jj + R_jj, the sum mhe_iekf_run forms: the mask is mhe_iekf_run's at the same
+ * prediction, and a screened row is out for every pass.  nis and loglik are pass 0's over the
+ * kept rows of the REWEIGHTED model: w and L of the sweep that used R~ at x_0 (not the innovation
+ * likelihood under R, unless every delta is +inf).  rej, n_iter and status are mhe_iekf_run's.
+ * Refusals and return codes are mhe_iekf_run's; in addition MHE_ERR_DIMS for a delta that is NaN
+ * or not > 0 when DELTA is NULL, and for delta != 0 when DELTA is given.  These precede the
+ * launch and the MHE_OK of an empty call (batch == 0 or steps == 0).
+ */
+typedef struct mhe_iekf_robust_args {
+  int32_t struct_size; /* = sizeof(mhe_iekf_robust_args) */
+  int32_t batch, steps;
+  double* mu;
+  double* S;
+  const double* U;
+  int64_t u_bstride;
+  const double* Z;
+  int64_t z_bstride;
+  const int32_t* nz;
+  int64_t nz_bstride;
+  const double* PAR;
+  int64_t par_bstride;
+  const double* Q;
+  const double* R;
+  int64_t r_bstride, r_sstride;
+  double* mu_hist;
+  double* S_hist;
+  int32_t* status;
+  double gate;
+  double* nis;
+  double* loglik;
+  int32_t* rej;
+  double tol;
+  int32_t* n_iter;
+  int32_t max_iter;
+  int32_t reserved0;
+  double delta;
+  const double* DELTA;
+  double* weights;
+} mhe_iekf_robust_args;
+
+int mhe_iekf_run_robust(const mhe_ekf_dims* dims, const mhe_iekf_robust_args* args, void* stream);
+
+/*
  * Fixed-interval (Rauch-Tung-Striebel) smoother over the history mhe_ekf_run wrote
  * (added to ABI v11; no existing struct or function changed).  One filter per lane;
  * a filter's result does not depend on the batch or on its place in it.

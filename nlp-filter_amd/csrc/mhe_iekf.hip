@@ -13,11 +13,15 @@
 // With max_iter = 1 the step is k_ekf's, term by term (S- below its diagonal is mirrored, so S is
 // bitwise symmetric).  Launch shape, per-wave LDS layout (plus
 // one n-vector for the iterate) and the wave-only barriers are k_ekf's: ONE WAVEFRONT PER
-// FILTER, four filters per workgroup.  One instance per plug-in pair serves every call: the
-// gate (+inf: no screening) and the optional statistics are k_ekf<.., true>'s, taken in pass 0.
+// FILTER, four filters per workgroup.  One instance per plug-in pair serves every mhe_iekf_run call:
+// the gate (+inf: no screening) and the optional statistics are k_ekf<.., true>'s, taken in pass 0.
+// A second instance per pair, k_iekf<.., ROBUST = true>, serves mhe_iekf_run_robust: the rows
+// reweighted in every pass (pseudo-Huber, see the kernel); the plain instances' code is unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "mhe.h"
 #include "mhe_ekf_models.h"
@@ -61,6 +65,17 @@ struct IekfArgs {
   int max_iter;  // 1..MAX_ITER
 };
 
+// mhe_iekf_run_robust's: the plain arguments, then the pseudo-Huber rows' (the plain instances'
+// kernel argument is IekfArgs itself, unchanged)
+struct IekfRobustArgs : IekfArgs {
+  double delta;         // every row's delta when DELTA is NULL; > 0, +inf allowed
+  const double* DELTA;  // optional, per row, laid out and strided as Z
+  double* weights;      // optional, omega of the last pass per row: pmax entries per step, laid out as the histories
+};
+
+template <bool ROBUST>
+using KernelArgs = std::conditional_t<ROBUST, IekfRobustArgs, IekfArgs>;
+
 constexpr double LOG_2PI = 1.8378770664093454836;
 
 // bits 0..rows-1 (rows <= 32)
@@ -88,8 +103,18 @@ struct WaveSmem {
 // nis, loglik and rej are pass 0's over the kept rows -- the innovation likelihood at the
 // prediction, what the EKF reports.  Status: 1 if any pass met a pivot that is not positive and
 // finite, 2 if nz > pmax at some step.
-template <class DYN, class MEAS>
-__global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
+//
+// ROBUST (mhe_iekf_run_robust): pseudo-Huber rows by iteratively reweighted Gauss-Newton.  In every
+// pass row j's residual r_j = z_j - h_j at the iterate gives t_j = r_j / delta_j,
+// s_j = sqrt(1 + t_j^2), g_j = sqrt(s_j), and the sweep runs on R~_jl = R_jl (g_j g_l) in place of
+// R: the weight omega_j = 1 / s_j as the covariance inflation D^-1/2 R D^-1/2, D = diag omega.  Lane
+// j owns g_j; the P build reads g_l from lane l's register.  delta = +inf gives s = g = 1 exactly
+// and R~ = R bitwise, so the run is the plain one's.  The gate tests the UNWEIGHTED diagonal
+// (H S- H^T)_jj + R_jj, the plain instances' sum, so the mask is the plain run's at the same
+// prediction; nis and loglik are pass 0's w and L of the REWEIGHTED model (R~ at x_0).  A zero
+// or NaN delta of a counted row makes a non-finite pivot: status 1.
+template <class DYN, class MEAS, bool ROBUST>
+__global__ __launch_bounds__(NWF * 64) void k_iekf(KernelArgs<ROBUST> a) {
   constexpr int n = DYN::n, m = DYN::m, q = MEAS::q;
   using WS = WaveSmem<n>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -147,6 +172,7 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
     bool corrected = valid;
     int it = 0;                 // passes made
     unsigned km = 0xffffffffu;  // the kept rows (wave-uniform), fixed by pass 0
+    double s = 1.0, g = 1.0;    // ROBUST: this lane's row, at the pass's iterate
     if (valid) {
       const long long rk = (long long)k * a.nmeas_rows_max + lane;  // row index within the instance
       const double* Rk = a.R + (long long)b * a.r_bstride + (long long)k * a.r_sstride;
@@ -157,6 +183,10 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
         for (int c = 0; c < q; ++c) par[c] = a.PAR[(long long)b * a.par_bstride + (rk * q + c) * a.es];
         z = a.Z[(long long)b * a.z_bstride + rk * a.es];
       }
+      double dl = INFINITY;
+      if constexpr (ROBUST) {
+        if (row) dl = a.DELTA ? a.DELTA[(long long)b * a.z_bstride + rk * a.es] : a.delta;
+      }
       for (;;) {
         // ---- measurement rows at the iterate; e = z - h - H (mu- - x_i)
         if (row) {
@@ -164,6 +194,11 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
           for (int c = 0; c < n; ++c) x[c] = X[c];
           MEAS::template row<n>(x, par, lane, nz, h, Hr);
           double e = z - h;
+          if constexpr (ROBUST) {
+            const double t = e / dl;
+            s = sqrt(1.0 + t * t);
+            g = sqrt(s);
+          }
           for (int c = 0; c < n; ++c) e -= Hr[c] * (MP[c] - x[c]);
           for (int c = 0; c < n; ++c) H[lane * n + c] = Hr[c];
           E[lane] = e;
@@ -182,10 +217,14 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
         double p[MAXP], t1[n], e = 0.0;
 #pragma unroll
         for (int j = 0; j < MAXP; ++j) {
-          double acc = 0.0;
+          double acc = 0.0, gg = 1.0;
+          if constexpr (ROBUST) gg = g * readlane_d(g, j);  // lanes that hold no row keep g = 1
           if (row && j < nz) {
             for (int l = 0; l < n; ++l) acc += T1[i * n + l] * H[j * n + l];
-            acc += Rk[i * a.nmeas_rows_max + j];
+            if constexpr (ROBUST)
+              acc += Rk[i * a.nmeas_rows_max + j] * gg;
+            else
+              acc += Rk[i * a.nmeas_rows_max + j];
           }
           p[j] = acc;
         }
@@ -195,8 +234,16 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
         if (it == 0) {
           // lane i tests its own diagonal entry of P, at the prediction
           double pd = 0.0;
+          if constexpr (ROBUST) {
+            // the unweighted P_ii, by the plain instances' sum
+            if (row) {
+              for (int l = 0; l < n; ++l) pd += T1[i * n + l] * H[i * n + l];
+              pd += Rk[i * a.nmeas_rows_max + i];
+            }
+          } else {
 #pragma unroll
-          for (int j = 0; j < MAXP; ++j) pd = (j == i) ? p[j] : pd;
+            for (int j = 0; j < MAXP; ++j) pd = (j == i) ? p[j] : pd;
+          }
           km = (unsigned)__ballot(row && !(pd > 0.0 && e * e / pd > a.gate));
           if (km == 0u) {  // every row screened out: predict-only
             corrected = false;
@@ -305,6 +352,12 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
       }
     }
     if (a.n_iter && lane == 0) a.n_iter[hist_at(a, b, k, 0, 1)] = corrected ? it : 0;
+    if constexpr (ROBUST) {
+      // omega of the last pass on the rows that were applied, 0 on every other row of the step
+      if (a.weights && lane < a.nmeas_rows_max)
+        a.weights[hist_at(a, b, k, lane, a.nmeas_rows_max)] =
+            (corrected && lane < nz && ((km >> (lane & 31)) & 1u)) ? 1.0 / s : 0.0;
+    }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (a.mu_hist)
@@ -317,30 +370,34 @@ __global__ __launch_bounds__(NWF * 64) void k_iekf(IekfArgs a) {
   if (a.status && lane == 0) a.status[b] = status;
 }
 
-template <class DYN, class MEAS>
-int launch(const IekfArgs& a, hipStream_t st) {
+template <class DYN, class MEAS, bool ROBUST>
+int launch(const KernelArgs<ROBUST>& a, hipStream_t st) {
   const int smem = NWF * WaveSmem<DYN::n>::total * (int)sizeof(double);
-  hipLaunchKernelGGL((k_iekf<DYN, MEAS>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
+  hipLaunchKernelGGL((k_iekf<DYN, MEAS, ROBUST>), dim3((a.batch + NWF - 1) / NWF), dim3(NWF * 64), smem, st, a);
   return hipGetLastError() == hipSuccess ? MHE_OK : MHE_ERR_HIP;
 }
 
-}  // namespace mhe_iekf
-
-extern "C" int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args, void* stream) {
-  using namespace mhe_iekf;
+// mhe_iekf_run (ARGS = mhe_iekf_args) and mhe_iekf_run_robust (mhe_iekf_robust_args: the same
+// fields in order, then delta, DELTA, weights): one set of refusals, all before the launch
+template <bool ROBUST, class ARGS>
+int run(const mhe_ekf_dims* dims, const ARGS* args, void* stream) {
   using namespace mhe_ekf;
   if (!dims || !args) return MHE_ERR_NULL;
   if (dims->struct_size != (int32_t)sizeof(mhe_ekf_dims)) return MHE_ERR_DIMS;  // stale / truncated binding
-  if (args->struct_size != (int32_t)sizeof(mhe_iekf_args)) return MHE_ERR_DIMS;
+  if (args->struct_size != (int32_t)sizeof(ARGS)) return MHE_ERR_DIMS;
   if (!(args->gate >= 0.0)) return MHE_ERR_DIMS;  // NaN or negative; 0 = no screening, +inf allowed
   if (!(args->tol >= 0.0)) return MHE_ERR_DIMS;   // NaN or negative
   if (args->max_iter < 1 || args->max_iter > MAX_ITER || args->reserved0 != 0) return MHE_ERR_DIMS;
+  if constexpr (ROBUST) {
+    // one delta for every row (> 0, +inf allowed), or an array and then delta == 0
+    if (args->DELTA ? args->delta != 0.0 : !(args->delta > 0.0)) return MHE_ERR_DIMS;
+  }
   const int32_t batch = args->batch, steps = args->steps;
-  if (batch < 0 || steps < 0 || dims->pmax < 1 || dims->pmax > mhe_iekf::MAXP) return MHE_ERR_DIMS;
+  if (batch < 0 || steps < 0 || dims->pmax < 1 || dims->pmax > MAXP) return MHE_ERR_DIMS;
   if (batch == 0 || steps == 0) return MHE_OK;
   if (!args->mu || !args->S || !args->Q || !args->nz || !args->Z || !args->R || (dims->m > 0 && !args->U))
     return MHE_ERR_NULL;
-  IekfArgs a = {};
+  KernelArgs<ROBUST> a = {};
   a.batch = batch; a.steps = steps; a.nmeas_rows_max = dims->pmax; a.dt = dims->dt;
   a.mu = args->mu; a.S = args->S; a.U = args->U; a.u_bstride = args->u_bstride; a.Z = args->Z;
   a.z_bstride = args->z_bstride; a.nz = args->nz; a.nz_bstride = args->nz_bstride; a.PAR = args->PAR;
@@ -349,6 +406,9 @@ extern "C" int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args,
   a.gate = args->gate != 0.0 ? args->gate : INFINITY;
   a.nis = args->nis; a.loglik = args->loglik; a.rej = args->rej;
   a.tol = args->tol; a.n_iter = args->n_iter; a.max_iter = args->max_iter;
+  if constexpr (ROBUST) {
+    a.delta = args->delta; a.DELTA = args->DELTA; a.weights = args->weights;
+  }
   a.hist_bi = dims->hist_batch_inner != 0;
   a.es = 1;
   if (dims->in_batch_inner) {  // U (steps, m, B), Z (steps, pmax, B), nz (steps, B), PAR (steps, pmax, q, B)
@@ -363,14 +423,25 @@ extern "C" int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args,
     if (dims->n != 5 || dims->m != 3) return MHE_ERR_MODEL;
     switch (dims->meas_model) {
       case MHE_EKF_MEAS_MULTI_PSEUDORANGE:
-        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<false>>(a, st);
+        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<false>, ROBUST>(a, st);
       case MHE_EKF_MEAS_MULTI_PSEUDORANGE_AND_BIAS:
-        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<true>>(a, st);
+        return launch<EkfGnssPosAndBias, EkfMultiPseudorange<true>, ROBUST>(a, st);
     }
   } else if (dims->dyn_model == MHE_EKF_DYN_DISCRETE_VEHICLE) {
     if (dims->n != 9 || dims->m != 2) return MHE_ERR_MODEL;
     if (!(dims->dyn_par[2] != 0.0 && dims->dyn_par[5] != 0.0)) return MHE_ERR_DIMS;  // M, I_Z unset
-    if (dims->meas_model == MHE_EKF_MEAS_VEHICLE_SENSORS) return launch<EkfDiscreteVehicle, EkfVehicleSensors>(a, st);
+    if (dims->meas_model == MHE_EKF_MEAS_VEHICLE_SENSORS)
+      return launch<EkfDiscreteVehicle, EkfVehicleSensors, ROBUST>(a, st);
   }
   return MHE_ERR_MODEL;
+}
+
+}  // namespace mhe_iekf
+
+extern "C" int mhe_iekf_run(const mhe_ekf_dims* dims, const mhe_iekf_args* args, void* stream) {
+  return mhe_iekf::run<false>(dims, args, stream);
+}
+
+extern "C" int mhe_iekf_run_robust(const mhe_ekf_dims* dims, const mhe_iekf_robust_args* args, void* stream) {
+  return mhe_iekf::run<true>(dims, args, stream);
 }

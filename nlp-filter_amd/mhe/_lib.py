@@ -62,6 +62,10 @@ class MheIekfArgs(_Sized):
     _fields_ = MheEkfArgs._fields_ + [("tol", c_dbl), ("n_iter", c_vp), ("max_iter", c_i32), ("reserved0", c_i32)]
 
 
+class MheIekfRobustArgs(_Sized):
+    _fields_ = MheIekfArgs._fields_ + [("delta", c_dbl), ("DELTA", c_vp), ("weights", c_vp)]
+
+
 class MheUkfArgs(_Sized):
     _fields_ = [("struct_size", c_i32), ("batch", c_i32), ("steps", c_i32), ("mu", c_vp), ("S", c_vp), ("U", c_vp),
                 ("u_bstride", c_i64), ("Z", c_vp), ("z_bstride", c_i64), ("nz", c_vp), ("nz_bstride", c_i64),
@@ -157,6 +161,7 @@ SIGNATURES = {
                                    c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mhe_ekf_run_args": (ctypes.c_int, [_PE, ctypes.POINTER(MheEkfArgs), c_vp]),
     "mhe_iekf_run": (ctypes.c_int, [_PE, ctypes.POINTER(MheIekfArgs), c_vp]),
+    "mhe_iekf_run_robust": (ctypes.c_int, [_PE, ctypes.POINTER(MheIekfRobustArgs), c_vp]),
     "mhe_ukf_run": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfArgs), c_vp]),
     "mhe_ukf_run_gated": (ctypes.c_int, [_PE, ctypes.POINTER(MheUkfGateArgs), c_vp]),
     "mhe_ekf_smooth": (ctypes.c_int, [_PE, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,

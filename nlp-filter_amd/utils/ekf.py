@@ -178,9 +178,35 @@ def _iter_values(iterations, iter_tol, method="auto"):
     return int(iterations), float(iter_tol)
 
 
+def _huber_value(huber, iterations):
+    """run_batch's `huber`: None, or (delta, DELTA) of mhe_iekf_robust_args -- (float > 0, None)
+    for a number (np.inf allowed) or (0.0, the array) for an array of Z's shape (its shape is
+    checked with the others').  A NumPy array is checked here for entries > 0; a torch tensor is
+    not read.  Anything else, and huber without iterations, raises ValueError."""
+    if huber is None:
+        return None
+    if iterations is None:
+        raise ValueError("huber needs iterations: the pseudo-Huber rows are the iterated filter's")
+    if isinstance(huber, (bool, np.bool_)):
+        raise ValueError(f"huber must be None, a float > 0 or an array of Z's shape, not {huber!r}")
+    if isinstance(huber, (int, float, np.integer, np.floating)):
+        if not float(huber) > 0.0:
+            raise ValueError(f"huber must be > 0 (np.inf allowed), not {huber!r}")
+        return float(huber), None
+    if isinstance(huber, np.ndarray):
+        if huber.ndim != 3 or huber.dtype.kind not in "fiu" or not bool(np.all(huber > 0)):
+            raise ValueError("a huber array has Z's shape and entries > 0 (np.inf allowed)")
+        return 0.0, huber
+    if hasattr(huber, "data_ptr") and hasattr(huber, "dim"):     # a torch tensor: not checked, as nz
+        if huber.dim() != 3:
+            raise ValueError("a huber array has Z's shape")
+        return 0.0, huber
+    raise ValueError(f"huber must be None, a float > 0 or an array of Z's shape, not {huber!r}")
+
+
 def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=None, stream=None,
               keep_history=True, method="auto", inputs="batch_outer", dyn_params=None, gate=None,
-              innovations=False, iterations=None, iter_tol=0.0):
+              innovations=False, iterations=None, iter_tol=0.0, huber=None):
     """Run B independent filters for T steps in one launch.
 
     mu0 (B,n), S0 (B,n,n), U (B,T,m), Z (B,T,pmax), nz (B,T) valid rows per step
@@ -229,10 +255,32 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     the innovations triple when that is present.  smooth_batch takes an iterated run's history
     as any other.  iterations=None is the call as it was.
 
+    huber: None, a float > 0 (np.inf allowed) or an array of Z's shape in Z's layout: pseudo-Huber
+    measurement rows (mhe_iekf_run_robust), the Huber-type Kalman correction by iteratively
+    reweighted Gauss-Newton.  It needs `iterations` (ValueError without).  delta is in the
+    measurement's own units, as the solver's meas_delta.  In every pass, with r = z - h(x_i):
+        t_j = r_j / delta_j,  s_j = sqrt(1 + t_j^2),  R~_jl = R_jl sqrt(s_j) sqrt(s_l),
+        P = H S- H^T + R~   and the pass, the stop rule and the final S are as above.
+    For a diagonal R this minimises sum_j 2 (delta_j^2 / R_jj) (s_j - 1) + the prior's term: a row
+    counts fully while |r_j| << delta_j and like |r_j| beyond it; for any R it is the covariance
+    inflation D^-1/2 R D^-1/2 with D = diag(omega), omega_j = 1 / s_j.  np.inf is the plain
+    iterated run, bitwise.  A NumPy array is checked on the host for entries > 0; a device tensor
+    is not checked, as nz: a zero or NaN entry of a counted row makes that filter's status 1.
+    gate goes with it: the screen is taken once, at the prediction, on the UNWEIGHTED
+    H_i S- H_i^T + R_ii, so the mask is the plain run's at the same prediction and a screened row
+    is out for every pass.  nis and loglik are then pass 0's over the kept rows of the REWEIGHTED
+    model (R~ at the prediction in place of R).  weights (B,T,pmax), omega of the last pass per
+    row and 0 for every row that was not applied (beyond nz, screened out, predict-only step), is
+    appended to the returned tuple last, after n_iter.  huber=None is the call as it was: its
+    result and the kernel it launches do not change.
+
     stream: a torch stream to order the work on (default: the current one); outputs
     belong to it (mhe.streams)."""
     gate = _gate_value(gate)
     iterations, iter_tol = _iter_values(iterations, iter_tol, method)
+    huber = _huber_value(huber, iterations)
+    if huber is not None and huber[1] is not None and tuple(huber[1].shape) != tuple(np.shape(Z)):
+        raise ValueError("a huber array has Z's shape, in Z's layout")
     import torch
 
     from mhe.streams import launch_stream
@@ -245,11 +293,11 @@ def run_batch(dyn_func, meas_func, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, device=
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     with launch_stream(stream, dev) as (s, cur):
         return _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history,
-                          method, inputs, dp, gate, bool(innovations), iterations, iter_tol)
+                          method, inputs, dp, gate, bool(innovations), iterations, iter_tol, huber)
 
 
 def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_pos, keep_history, method,
-               inputs, dp, gate=0.0, innovations=False, iterations=None, iter_tol=0.0):
+               inputs, dp, gate=0.0, innovations=False, iterations=None, iter_tol=0.0, huber=None):
     """run_batch on torch stream s (staging and allocation ordered on s)."""
     import torch
 
@@ -278,6 +326,9 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
     if mu.shape != (B, n) or S.shape != (B, n, n) or Ut.shape != shapes[0] or nzt.shape != shapes[1] \
             or Pt.shape != shapes[2] or Zt.shape != shapes[3] or Qt.shape != (n, n):
         raise ValueError("run_batch: inconsistent shapes")
+    Dt = d(huber[1]) if huber is not None and huber[1] is not None else None     # laid out and strided as Z
+    if Dt is not None and Dt.shape != Zt.shape:
+        raise ValueError("a huber array has Z's shape, in Z's layout")
     if Rt.dim() == 3:
         r_b, r_s = 0, pmax * pmax
         if Rt.shape != (T, pmax, pmax):
@@ -312,14 +363,21 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
                       for dt_ in (torch.float64, torch.float64, torch.int32)) if innovations else ()
         nis, ll, rej = stats if innovations else (None, None, None)
         stats += (torch.empty((T, B), dtype=torch.int32, device=dev),)      # n_iter, last
-        args = _lib.MheIekfArgs(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
-                                Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
-                                PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
-                                r_bstride=r_b, r_sstride=r_s, mu_hist=_ptr(mh_st), S_hist=_ptr(Sh_st),
-                                status=st.data_ptr(), gate=gate, nis=_ptr(nis), loglik=_ptr(ll), rej=_ptr(rej),
-                                tol=iter_tol, n_iter=stats[-1].data_ptr(), max_iter=iterations)
-        rc = lib.mhe_iekf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
-        _lib.check(rc, "mhe_iekf_run")
+        kw = dict(batch=B, steps=T, mu=mu.data_ptr(), S=S.data_ptr(), U=Ut.data_ptr(), u_bstride=T * m,
+                  Z=Zt.data_ptr(), z_bstride=T * pmax, nz=nzt.data_ptr(), nz_bstride=T,
+                  PAR=Pt.data_ptr(), par_bstride=T * pmax * q, Q=Qt.data_ptr(), R=Rt.data_ptr(),
+                  r_bstride=r_b, r_sstride=r_s, mu_hist=_ptr(mh_st), S_hist=_ptr(Sh_st),
+                  status=st.data_ptr(), gate=gate, nis=_ptr(nis), loglik=_ptr(ll), rej=_ptr(rej),
+                  tol=iter_tol, n_iter=stats[-1].data_ptr(), max_iter=iterations)
+        if huber is None:
+            args = _lib.MheIekfArgs(**kw)
+            rc = lib.mhe_iekf_run(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+            _lib.check(rc, "mhe_iekf_run")
+        else:
+            w_st = torch.empty((T, pmax, B), dtype=torch.float64, device=dev)   # every entry is written
+            args = _lib.MheIekfRobustArgs(delta=huber[0], DELTA=_ptr(Dt), weights=w_st.data_ptr(), **kw)
+            rc = lib.mhe_iekf_run_robust(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
+            _lib.check(rc, "mhe_iekf_run_robust")
     elif gate == 0.0 and not innovations:
         rc = lib.mhe_ekf_run(ctypes.byref(dims), B, T, _ptr(mu), _ptr(S), _ptr(Ut), T * m, _ptr(Zt), T * pmax,
                              _ptr(nzt), T, _ptr(Pt), T * pmax * q, _ptr(Qt), _ptr(Rt), r_b, r_s, _ptr(mh_st),
@@ -338,10 +396,11 @@ def _run_batch(did, n, m, mid, q, dev, s, cur, mu0, S0, U, Z, nz, Q, R, dt, sat_
                                status=st.data_ptr(), gate=gate, nis=_ptr(nis), loglik=_ptr(ll), rej=_ptr(rej))
         rc = lib.mhe_ekf_run_args(ctypes.byref(dims), ctypes.byref(args), ctypes.c_void_p(s.cuda_stream))
         _lib.check(rc, "mhe_ekf_run_args")
-    keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st, *stats)
+    robust = () if huber is None else (w_st,)
+    keep_alive(s, cur, mu, S, Ut, Zt, nzt, Pt, Qt, Rt, mh_st, Sh_st, st, Dt, *stats, *robust)
     mh = mh_st.permute(2, 0, 1) if keep_history else None
     Sh = Sh_st.permute(3, 0, 1, 2) if keep_history else None
-    return (mh, Sh, mu, S, st) + tuple(t.permute(1, 0) for t in stats)
+    return (mh, Sh, mu, S, st) + tuple(t.permute(1, 0) for t in stats) + tuple(t.permute(2, 0, 1) for t in robust)
 
 
 def _hist_storage(t, w):
@@ -647,7 +706,7 @@ class EKF(object):
         models(dyn_func, meas_func)  # fail at construction for unregistered plug-ins
 
     def update(self, u, z, Q, R, dyn_func_params=None, meas_func=None, meas_func_params=None, gate=None,
-               iterations=None, iter_tol=0.0):
+               iterations=None, iter_tol=0.0, huber=None):
         """One predict (+ correct when z is given) step, utils/ekf.py:20-38.
 
         gate (run_batch's; np.inf: statistics only): rows of z whose normalised innovation
@@ -660,9 +719,20 @@ class EKF(object):
         H_i (mu- - x_i)), until the step's max-norm is not above iter_tol (absolute, in the
         state's units; keep it above the rows' rounding floor, about 1e-8 m for pseudoranges)
         or `iterations` passes are made; the object then holds ``n_iter`` (int), the passes
-        this update made (0: no correction)."""
+        this update made (0: no correction).
+
+        huber (run_batch's; needs iterations): a float > 0 (np.inf allowed) or one per row of z --
+        pseudo-Huber rows; the object then holds ``weights`` (one float per row of z: omega of
+        the last pass, 0 for a row that was screened out or not applied).  Without the keyword
+        nothing changes and no ``weights`` is set."""
         gv = _gate_value(gate)
         iterations, iter_tol = _iter_values(iterations, iter_tol)
+        if huber is not None and not isinstance(huber, (bool, np.bool_, int, float, np.integer, np.floating)):
+            huber = np.asarray(huber)
+            if huber.dtype.kind not in "fiu" or huber.ndim != 1:
+                raise ValueError("huber must be a float > 0 or one float > 0 per row of z")
+            huber = huber.astype(np.float64).reshape(1, 1, -1)
+        hv = _huber_value(huber, iterations)
         meas = meas_func if meas_func is not None else self.measurement
         (_, n, m), (_, extra, q) = models(self.dynamics, meas)
         dt = float((dyn_func_params or {})["dt"])
@@ -687,6 +757,12 @@ class EKF(object):
         kw = {} if gate is None else dict(gate=gv, innovations=True)
         if iterations is not None:
             kw.update(iterations=iterations, iter_tol=iter_tol)
+        if hv is not None:
+            if hv[1] is not None and z is None:
+                hv = (float(np.min(hv[1])), None)       # no row: nothing to weigh
+            elif hv[1] is not None and hv[1].shape != Z.shape:
+                raise ValueError("huber and z disagree in size")
+            kw.update(huber=hv[0] if hv[1] is None else hv[1])
         out = run_batch(self.dynamics, meas, mu0, S0, u_, Z, np.full((1, 1), nz, np.int32),
                         np.asarray(Q, dtype=np.float64), Rm, dt, P, keep_history=False,
                         dyn_params=dyn_func_params, **kw)
@@ -698,6 +774,8 @@ class EKF(object):
             word = int(out[7][0, 0].item()) & 0xFFFFFFFF
             self.rejected = np.array([bool((word >> i) & 1) for i in range(nz)], dtype=bool)
         if iterations is not None:
-            self.n_iter = int(out[-1][0, 0].item())
+            self.n_iter = int(out[-2 if hv is not None else -1][0, 0].item())
+        if hv is not None:
+            self.weights = out[-1][0, 0, :nz].cpu().numpy().astype(np.float64)
         self.mu = mu[0].cpu().numpy()
         self.S = S[0].cpu().numpy()

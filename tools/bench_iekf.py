@@ -1,6 +1,6 @@
 """Cost of the iterated EKF (mhe_iekf_run, k_iekf) beside the same build's wave-method EKF (k_ekf).
 
-    python tools/bench_iekf.py [gnss|autocar] [B] [reps] [--out FILE]
+    python tools/bench_iekf.py [gnss|autocar] [B] [reps] [--out FILE] [--robust]
 
 Workloads: the gnss_stationary recipe (n = 5, 12 slots, 51 steps) and the autonomous-car recipe
 (n = 9, 300 steps, 8-11 rows at every 10th step), B = 65536 filters by default, inputs
@@ -16,6 +16,18 @@ Launch kinds:
     iter1         iterations=1
     iter3         iterations=3, iter_tol=0: two further passes at every corrected step
     cold8         iterations=8, iter_tol=TOL on the cold prior (the mean pass count is recorded)
+
+--robust adds the pseudo-Huber rows (mhe_iekf_run_robust, huber=) and its outlier recipe, the one of
+tools/bench_ekf_gate.py: a seeded 8 % of the valid rows shifted by +400 m, the consistent prior:
+
+    robust_inf3   iterations=3, iter_tol=0, huber=inf: iter3's work plus the reweighting alone
+    out_plain     iterations=16, iter_tol=TOL on the outlier inputs
+    out_gate      the same with gate=10.83
+    out_huber     the same with huber=DELTA (15, the measurement's units), no gate
+    out_both      the same with huber=DELTA and gate=10.83
+
+and records robust_inf3 / iter3, and for the out_* kinds the passes per corrected step and (gnss)
+the position error after the last step.
 
 Timing: HIP events around `reps` launches of one kind; the kinds alternate within a window, three
 windows, the median per kind is reported.  One JSON line per run is printed and appended to --out
@@ -38,6 +50,7 @@ import utils.ekf as ekf  # noqa: E402
 import utils.gnss as gnss  # noqa: E402
 import utils.vehicle as veh  # noqa: E402
 
+ROBUST = "--robust" in sys.argv
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "iekf.jsonl")
 if "--out" in sys.argv:
@@ -46,6 +59,7 @@ WHICH = argv[0] if argv else "gnss"
 B = int(argv[1]) if len(argv) > 1 else 65536
 REPS = int(argv[2]) if len(argv) > 2 else 3
 TOL = {"gnss": 1e-4, "autocar": 1e-6}[WHICH]
+GATE, SHIFT, FRACTION, DELTA = 10.83, 400.0, 0.08, 15.0
 dev = torch.device("cuda", 0)
 G = os.path.join(ROOT, "tests", "golden")
 
@@ -116,18 +130,33 @@ def pos_err(mh):
             "last_max": float(e[1].max().item())}
 
 
+if ROBUST:
+    valid = torch.arange(pmax, device=dev)[None, :, None] < nz[:, None, :]
+    planted = valid & (torch.rand(Z.shape, dtype=torch.float64, device=dev, generator=gen) < FRACTION)
+    Z8 = Z + SHIFT * planted
+
+    def run8(**kw):
+        return ekf.run_batch(dyn, meas, mu0, S0, U, Z8, nz, Q, R, dparams["dt"], sat, inputs="batch_inner",
+                             dyn_params=dparams, iterations=16, iter_tol=TOL, **kw)
+
+    KINDS.update({"robust_inf3": lambda: run(iterations=3, iter_tol=0.0, huber=float("inf")),
+                  "out_plain": lambda: run8(),
+                  "out_gate": lambda: run8(gate=GATE),
+                  "out_huber": lambda: run8(huber=DELTA),
+                  "out_both": lambda: run8(huber=DELTA, gate=GATE)})
+
 facts = {}
 for name, fn in KINDS.items():      # warm-up, and what each kind did
     out = fn()
     torch.cuda.synchronize()
     facts[name] = {"status_nonzero": int((out[4] != 0).sum().item())}
     if len(out) > 5:
-        cnt = out[-1]
+        cnt = out[-2] if name in ("robust_inf3", "out_huber", "out_both") else out[-1]   # weights come after n_iter
         done = cnt > 0
         facts[name].update(corrected_steps=int(done.sum().item()),
                            mean_passes=float(cnt[done].double().mean().item()) if bool(done.any()) else 0.0,
                            max_passes=int(cnt.max().item()))
-    if WHICH == "gnss" and name == "cold8":
+    if WHICH == "gnss" and (name == "cold8" or name.startswith("out_")):
         facts[name]["position_error_m"] = pos_err(out[0])
     del out
 if WHICH == "gnss":
@@ -158,6 +187,9 @@ rec = {"metric": "iterated-EKF filter-steps/s by launch kind", "workload": WHICH
        "iter1_over_ekf_wave": med["iter1"] / med["ekf_wave"],
        "k_ekf_correct_phase_ms": correct, "further_pass_ms": further,
        "further_pass_over_k_ekf_correct_phase": further / correct if correct > 0 else None}
+if ROBUST:
+    rec.update(robust_inf3_over_iter3=med["robust_inf3"] / med["iter3"], outliers={"shift_m": SHIFT, "fraction": FRACTION},
+               gate=GATE, huber_delta=DELTA, planted_rows=int(planted.sum().item()))
 line = json.dumps(rec)
 print(line)
 os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Compare the device code of two source trees: tools/isa_diff.py TREE_A TREE_B [UNIT.hip ...]
+"""Compare the device code of two source trees: tools/isa_diff.py [--map REGEX=REPL] TREE_A TREE_B [UNIT.hip ...]
 Compiles every .hip unit of the Makefile's SRCS in both trees with the Makefile's
 flags plus --cuda-device-only -S, splits the assembly into functions and reports,
 per unit, the symbols only in A, only in B, with a different body, or with a
 different kernel descriptor (.amdhsa_kernel block: VGPR/SGPR, LDS, scratch).
-Exit status 0 only if B equals A up to pure removals.  Text equality only."""
+Exit status 0 only if B equals A up to pure removals.  Text equality only.
+--map REGEX=REPL rewrites tree A's assembly first: for a kernel whose mangled name moved (a
+template parameter added) while its code is claimed unchanged."""
 import re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -59,10 +61,20 @@ def split(text):
 
 
 def main():
-    a, b = sys.argv[1:3]
-    units = sys.argv[3:] or recipe(a)[2]
+    argv, maps = sys.argv[1:], []
+    while argv and argv[0] == "--map":
+        maps.append(argv[1].split("=", 1))
+        argv = argv[2:]
+    a, b = argv[:2]
+    units = argv[2:] or recipe(a)[2]
+
+    def one(tu):
+        text = asm(*tu)
+        for pat, repl in (maps if tu[0] == a else []):
+            text = re.sub(pat, repl, text)
+        return split(text)
     with ThreadPoolExecutor(8) as ex:       # at most 8 compiles at a time
-        outs = list(ex.map(lambda tu: split(asm(*tu)), [(t, u) for u in units for t in (a, b)]))
+        outs = list(ex.map(one, [(t, u) for u in units for t in (a, b)]))
     bad = 0
     for i, u in enumerate(units):
         (fa, da), (fb, db) = outs[2 * i], outs[2 * i + 1]

@@ -50,6 +50,9 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #endif
 constexpr int NW = MHE_NW;
 constexpr int NTHREADS = NW * 64;
+// threads per row of the mat-vec phases (see "model phases"), and the rows of one pass
+constexpr int TPR = NW >= 8 ? 4 : 2;
+constexpr int MV_ROWS = NTHREADS / TPR;
 constexpr int MAX_NT = 13;         // padded system <= 208 (register-resident path)
 // The NT(NT-1)/2 off-diagonal tiles live in MFMA accumulator registers (20
 // slots per wave at NT = 13, 160 VGPRs); the NT diagonal tiles live in LDS.
@@ -68,15 +71,50 @@ extern int g_opt_lsm_group;  // defined in mhe_ls.hip: forces k_ls_multi's group
 
 // ------------------------------------------------------------ layouts
 struct ConstLayout {
-  size_t D, Dt, Phi, PhiT, cw, Qw, Pw, Rw, Cc, DA, DB, DAc, DBc, total;  // byte offsets
+  size_t D, Dt, Phi, PhiT, cw, Qw, Pw, Rw, Cc, DA, DB, DAc, DBc, NMS, GRS, total;  // byte offsets
+  int nmu, grv;  // 16-byte elements per lane and wave of NMS / GRS (0: the stream is absent)
 };
 
 __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // Every constants buffer starts with this header: the layout stamp at offset 0.
 constexpr size_t CONST_HEADER = 256;
+// Revision of the layouts below, part of the stamp (const_tag): 2 = with the mat-vec streams
+// NMS and GRS behind the compact blocks
+constexpr int CONST_LAYOUT_REV = 2;
 
-__host__ __device__ inline ConstLayout const_layout(int P, int M, int n, int p, int NT) {
+// The mat-vec streams (node_meas_phase, grad_phase): the tables' elements in the order the
+// lanes consume them, one 16-byte element per lane and load, so that a wave instruction reads
+// ONE contiguous, 128-B aligned KiB.  A wave's 64 lanes are 16 rows x TPR = 4 parts, which
+// holds for every NW >= 8; the phases assert TPR == 4.
+constexpr int STREAM_PIECE = 64 * 16;  // bytes per wave instruction
+// NMS[wave][u][lane] = {Dt[q + 4u][row], PhiT[q + 4u][row]}, q = lane / 16, row = 16 wave +
+// lane % 16 clamped to P - 1 / M - 1: the one-pass branch only (P, M <= MV_ROWS)
+__host__ __device__ inline int nms_terms(int P, int M) {
+  return (P <= MV_ROWS && M <= MV_ROWS) ? (P + TPR - 1) / TPR : 0;
+}
+// GRS[pass][wave][v][lane] = {T[sub + 4v][node], T[sub + 4v + 2][node]}, T = D (lanes 0..31)
+// or Phi (lanes 32..63), sub = (lane / 16) % 2, node = MV_ROWS pass + 16 wave + lane % 16
+// clamped to P - 1; 0 beyond the table's last row
+__host__ __device__ inline int grs_pairs(int P, int M) { return ((P > M ? P : M) + 3) / 4; }
+__host__ __device__ inline int grs_passes(int P) { return (P + MV_ROWS - 1) / MV_ROWS; }
+
+// Which instances read the streams: state dimensions 2 and 4.  A 16-byte load needs an
+// aligned 4-VGPR tuple per staged element, and the instances of the other dimensions
+// (n = 1, 5, 6, 10: already over the register edge, 44 to 1336 B/lane of scratch) paid for
+// it with more scratch; they keep the loops on the tables, and
+// their constants carry no streams.  -DMHE_MV_STREAMS=<mask> (make variant) builds the A/B
+// steps of that round: bit 0 NMS, bit 1 GRS.
+#ifndef MHE_MV_STREAMS
+#define MHE_MV_STREAMS 3
+#endif
+__host__ __device__ constexpr bool mv_stream(int n, int bit) {
+  return (n == 2 || n == 4) && ((MHE_MV_STREAMS >> bit) & 1);
+}
+
+// streams = false: the layout of a kernel that runs the mat-vec phases on D / Phi themselves
+// (k_gn_general, whose Phi holds epoch rows)
+__host__ __device__ inline ConstLayout const_layout(int P, int M, int n, int p, int NT, bool streams = true) {
   ConstLayout L;
   size_t o = CONST_HEADER;
   const size_t ntiles = size_t(NT) * (NT + 1) / 2;
@@ -96,6 +134,13 @@ __host__ __device__ inline ConstLayout const_layout(int P, int M, int n, int p, 
   // in the layout that spread_dblock turns into the tile's C layout (VALU swaps)
   L.DAc = o;  o = align256(o + sizeof(double) * ntiles * 64);
   L.DBc = o;  o = align256(o + sizeof(double) * ntiles * 64);
+  // the streams, last, so that no offset above moves.  The phases form their byte offsets
+  // in int, like every raw buffer load of this buffer (cbuf_rsrc takes its size as an int):
+  // the register path's P n <= 208 keeps the whole buffer within a few MB
+  L.nmu = streams && mv_stream(n, 0) ? nms_terms(P, M) : 0;
+  L.grv = streams && mv_stream(n, 1) ? grs_pairs(P, M) : 0;
+  L.NMS = o;  o = align256(o + size_t(STREAM_PIECE) * NW * L.nmu);
+  L.GRS = o;  o = align256(o + size_t(STREAM_PIECE) * NW * L.grv * grs_passes(P));
   L.total = o;
   return L;
 }
@@ -246,6 +291,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t cbuf_rsrc(const char* cbuf, si
 __device__ __forceinline__ double bload(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   const mhe_u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
   return __builtin_bit_cast(double, v);
+}
+// Two consecutive doubles at a 16-byte aligned offset: one 16-byte request per lane
+typedef unsigned int mhe_u4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ d2 bload2(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
+  const mhe_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+  return __builtin_bit_cast(d2, v);
 }
 
 // dpp_d, pair_combine, wave_sum: mhe_wave.h (shared with mhe_ls.hip)
@@ -516,8 +568,7 @@ __device__ __forceinline__ void init_rowmask(int* rowm, int wave, int lane, int 
 // Mat-vec phases use TPR threads per row (4 with 8 waves): each sums every
 // TPR-th term of the row with an 8-deep unrolled loop (8 independent L2 loads
 // in flight), the parts are combined with lane swaps.  The tables (D, D^T, Phi,
-// Phi^T) are shared by every workgroup and L2-resident.
-constexpr int TPR = NW >= 8 ? 4 : 2;
+// Phi^T) are shared by every workgroup and L2-resident.  (TPR: at the top of this file.)
 
 // threadIdx.x through an opaque move: values derived from it inside a phase
 // are recomputed per phase instead of being hoisted out of the Gauss-Newton
@@ -829,45 +880,78 @@ __device__ __forceinline__ double node_meas_phase(const GnArgs& a, const ConstLa
   if constexpr (SKIP)
     if (16 * __builtin_amdgcn_readfirstlane(tid >> 6) >= (a.P > a.M ? a.P : a.M)) return 0.0;
   const int part = (tid >> 4) & 3, r = (tid >> 6) * 16 + (tid & 15);
-  const int kk = r < a.P ? r : a.P - 1, ii = r < a.M ? r : a.M - 1;
   double dx[n], xi[n];
 #pragma unroll
   for (int c = 0; c < n; ++c) dx[c] = xi[c] = 0.0;
   const int len = a.P;
-  // byte offsets of Dt[j][kk] and PhiT[j][ii]; per term u the uniform offsets u TPR ld 8
-  int o1 = (int)CL.Dt + (part * a.P + kk) * 8, o2 = (int)CL.PhiT + (part * a.M + ii) * 8;
-  const int s1 = TPR * a.P * 8, s2 = TPR * a.M * 8;
-  int j = part;
+  if constexpr (mv_stream(n, 0)) {
+    // term j = part + TPR u of this lane is element u of its NMS column, {Dt[j][kk],
+    // PhiT[j][ii]} (k_copy_consts): one 16-byte load per term for both tables, a wave
+    // instruction one contiguous KiB.  A lane adds exactly the terms j < P it always added,
+    // in the same order (the elements past a part's last term are never read).
+    int o = (int)CL.NMS + __builtin_amdgcn_readfirstlane(tid >> 6) * CL.nmu * STREAM_PIECE + (tid & 63) * 16;
+    int j = part;
 #pragma unroll 1
-  for (; j + TPR * 7 < len; j += TPR * 8) {
-    double m1[8], m2[8];
+    for (; j + TPR * 7 < len; j += TPR * 8) {
+      d2 m[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      m1[u] = bload(rs, o1, u * s1);
-      m2[u] = bload(rs, o2, u * s2);
+      for (int u = 0; u < 8; ++u) m[u] = bload2(rs, o, u * STREAM_PIECE);
+      o += 8 * STREAM_PIECE;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int c = 0; c < n; ++c) {
+          const double x = Xs[(j + TPR * u) * n + c];
+          dx[c] += m[u].x * x;
+          xi[c] += m[u].y * x;
+        }
     }
-    o1 += 8 * s1;
-    o2 += 8 * s2;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
+    for (; j < len; j += TPR) {
+      const d2 m = bload2(rs, o, 0);
+      o += STREAM_PIECE;
 #pragma unroll
       for (int c = 0; c < n; ++c) {
-        const double x = Xs[(j + TPR * u) * n + c];
-        dx[c] += m1[u] * x;
-        xi[c] += m2[u] * x;
+        dx[c] += m.x * Xs[j * n + c];
+        xi[c] += m.y * Xs[j * n + c];
       }
-  }
-  for (; j < len; j += TPR) {
-    const double m1 = bload(rs, o1, 0), m2 = bload(rs, o2, 0);
-    o1 += s1;
-    o2 += s2;
+    }
+  } else {
+    const int kk = r < a.P ? r : a.P - 1, ii = r < a.M ? r : a.M - 1;
+    // byte offsets of Dt[j][kk] and PhiT[j][ii]; per term u the uniform offsets u TPR ld 8
+    int o1 = (int)CL.Dt + (part * a.P + kk) * 8, o2 = (int)CL.PhiT + (part * a.M + ii) * 8;
+    const int s1 = TPR * a.P * 8, s2 = TPR * a.M * 8;
+    int j = part;
+#pragma unroll 1
+    for (; j + TPR * 7 < len; j += TPR * 8) {
+      double m1[8], m2[8];
 #pragma unroll
-    for (int c = 0; c < n; ++c) {
-      dx[c] += m1 * Xs[j * n + c];
-      xi[c] += m2 * Xs[j * n + c];
+      for (int u = 0; u < 8; ++u) {
+        m1[u] = bload(rs, o1, u * s1);
+        m2[u] = bload(rs, o2, u * s2);
+      }
+      o1 += 8 * s1;
+      o2 += 8 * s2;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int c = 0; c < n; ++c) {
+          const double x = Xs[(j + TPR * u) * n + c];
+          dx[c] += m1[u] * x;
+          xi[c] += m2[u] * x;
+        }
+    }
+    for (; j < len; j += TPR) {
+      const double m1 = bload(rs, o1, 0), m2 = bload(rs, o2, 0);
+      o1 += s1;
+      o2 += s2;
+#pragma unroll
+      for (int c = 0; c < n; ++c) {
+        dx[c] += m1 * Xs[j * n + c];
+        xi[c] += m2 * Xs[j * n + c];
+      }
     }
   }
-  static_assert(TPR == 4, "the row reductions below assume 4 parts per row");
+  static_assert(TPR == 4, "the row reductions below and the NMS stream assume 4 parts per row");
 #pragma unroll
   for (int c = 0; c < n; ++c) {
     dx[c] = row_pair_sum(dx[c]);  // (part 0 + part 1), (part 2 + part 3)
@@ -919,7 +1003,9 @@ __device__ __forceinline__ double prior_cost(const GnArgs& a, const double* Pw, 
 // trailing zero fill -- see node_meas_phase
 // OZ: the zero of the trailing fill is opaque (as a constant it is hoisted out of the Gauss-Newton
 // loop and, in the instances that run first_panel, spilled across it)
-template <class DYN, bool PW = true, bool SKIP = false, bool OZ = false>
+// STREAM: the D and Phi columns come from the GRS stream of the constants where the instance
+// reads streams (mv_stream); false: from D and Phi themselves (k_gn_general, whose layout has none)
+template <class DYN, bool PW = true, bool SKIP = false, bool OZ = false, bool STREAM = true>
 __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout& CL, const SmemLayout& SL, double* sm, int b) {
   constexpr int n = DYN::n;
   const __amdgpu_buffer_rsrc_t rs = cbuf_rsrc(a.cbuf, CL.total);
@@ -948,26 +1034,62 @@ __device__ __forceinline__ double grad_phase(const GnArgs& a, const ConstLayout&
     double s[n];
 #pragma unroll
     for (int c = 0; c < n; ++c) s[c] = 0.0;
-    // D and Phi share the row stride P: byte offset of Mt[k][jj], uniform step per term
-    int om = (int)(phi ? CL.Phi : CL.D) + (sub * a.P + jj) * 8;
-    const int sm8 = HP * a.P * 8;
     int k = sub;
+    if constexpr (STREAM && mv_stream(n, 1)) {
+      // the terms k = sub + HP t of this lane, two by two: element v of its GRS column is
+      // {Mt[sub + 4v][jj], Mt[sub + 4v + 2][jj]} (k_copy_consts).  The terms and their order
+      // are those of the loop on the table itself below; of a last pair with one term the
+      // first half alone is loaded.
+      int og = (int)CL.GRS + (j0 / MV_ROWS * NW + __builtin_amdgcn_readfirstlane(tid >> 6)) * CL.grv * STREAM_PIECE +
+               (tid & 63) * 16;
 #pragma unroll 1
-    for (; k + HP * 7 < len; k += HP * 8) {
-      double mv[8];
+      for (; k + HP * 7 < len; k += HP * 8) {
+        d2 mv[4];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) mv[u] = bload(rs, om, u * sm8);
-      om += 8 * sm8;
+        for (int u = 0; u < 4; ++u) mv[u] = bload2(rs, og, u * STREAM_PIECE);
+        og += 4 * STREAM_PIECE;
 #pragma unroll
-      for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < 4; ++u) {
 #pragma unroll
-        for (int c = 0; c < n; ++c) s[c] += mv[u] * vec[(k + HP * u) * n + c];
-    }
-    for (; k < len; k += HP) {
-      const double mv = bload(rs, om, 0);
-      om += sm8;
+          for (int c = 0; c < n; ++c) s[c] += mv[u].x * vec[(k + HP * 2 * u) * n + c];
 #pragma unroll
-      for (int c = 0; c < n; ++c) s[c] += mv * vec[k * n + c];
+          for (int c = 0; c < n; ++c) s[c] += mv[u].y * vec[(k + HP * (2 * u + 1)) * n + c];
+        }
+      }
+      for (; k + HP < len; k += HP * 2) {
+        const d2 mv = bload2(rs, og, 0);
+        og += STREAM_PIECE;
+#pragma unroll
+        for (int c = 0; c < n; ++c) s[c] += mv.x * vec[k * n + c];
+#pragma unroll
+        for (int c = 0; c < n; ++c) s[c] += mv.y * vec[(k + HP) * n + c];
+      }
+      if (k < len) {
+        const double mv = bload(rs, og, 0);
+#pragma unroll
+        for (int c = 0; c < n; ++c) s[c] += mv * vec[k * n + c];
+      }
+    } else {
+      // D and Phi share the row stride P: byte offset of Mt[k][jj], uniform step per term
+      int om = (int)(phi ? CL.Phi : CL.D) + (sub * a.P + jj) * 8;
+      const int sm8 = HP * a.P * 8;
+#pragma unroll 1
+      for (; k + HP * 7 < len; k += HP * 8) {
+        double mv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) mv[u] = bload(rs, om, u * sm8);
+        om += 8 * sm8;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+          for (int c = 0; c < n; ++c) s[c] += mv[u] * vec[(k + HP * u) * n + c];
+      }
+      for (; k < len; k += HP) {
+        const double mv = bload(rs, om, 0);
+        om += sm8;
+#pragma unroll
+        for (int c = 0; c < n; ++c) s[c] += mv * vec[k * n + c];
+      }
     }
     static_assert(HP == 2, "the row reductions below assume TPR == 4");
 #pragma unroll

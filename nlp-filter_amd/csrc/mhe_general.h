@@ -36,7 +36,7 @@ struct FgConst {
 };
 __host__ __device__ inline FgConst fg_const_layout(int P, int M, int n, int NT, int nc) {
   FgConst L;
-  L.C = const_layout(P, M, n, 1, NT);
+  L.C = const_layout(P, M, n, 1, NT, false);
   size_t o = L.C.total;
   const int Mr = M > 0 ? M : 1, ncr = nc > 0 ? nc : 1;
   L.erow = o; o = align256(o + sizeof(int) * (Mr + 1));  // first row of each epoch, erow[E] = M
@@ -195,7 +195,7 @@ __device__ __forceinline__ double fg_resid(const GnArgs& ae, const FgConst& FC, 
     }
   }
   __syncthreads();
-  cost += grad_phase<DYN, true>(ae, CL, SL, sm, b);
+  cost += grad_phase<DYN, true, false, false, false>(ae, CL, SL, sm, b);
   return cost;
 }
 

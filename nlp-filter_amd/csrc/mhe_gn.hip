@@ -53,6 +53,26 @@ __global__ void k_copy_consts(int P, int M, int n, int p, int NT, const double* 
     ((double*)(cbuf + CL.Pw))[e] = Pw ? Pw[e] : 0.0;
   }
   for (int e = gid; e < M * p * p; e += stride) ((double*)(cbuf + CL.Rw))[e] = Rw[e];
+  // The mat-vec streams (const_layout): what lane `lane` of wave w reads as its element u / v.
+  // Padding rows hold the clamped row's values, as the clamped index read from the tables.
+  double* oN = (double*)(cbuf + CL.NMS);
+  for (int e = gid; e < NW * CL.nmu * 64; e += stride) {
+    const int lane = e & 63, u = (e >> 6) % CL.nmu, w = (e >> 6) / CL.nmu;
+    const int j = (lane >> 4) + TPR * u, r = 16 * w + (lane & 15);
+    const int kk = r < P ? r : P - 1, ii = r < M ? r : M - 1;
+    oN[2 * e] = j < P ? D[kk * P + j] : 0.0;                 // Dt[j][kk]
+    oN[2 * e + 1] = j < P && M > 0 ? Phi[ii * P + j] : 0.0;  // PhiT[j][ii]
+  }
+  double* oG = (double*)(cbuf + CL.GRS);
+  for (int e = gid; e < grs_passes(P) * NW * CL.grv * 64; e += stride) {
+    const int lane = e & 63, v = (e >> 6) % CL.grv, pw = (e >> 6) / CL.grv;  // pw = NW pass + wave
+    const int q = lane >> 4, node = 16 * pw + (lane & 15), jj = node < P ? node : P - 1;
+    const bool phi = q >= TPR / 2;
+    const double* T = phi ? Phi : D;
+    const int len = phi ? M : P, k0 = q % (TPR / 2) + 4 * v, k1 = k0 + 2;
+    oG[2 * e] = k0 < len ? T[k0 * P + jj] : 0.0;
+    oG[2 * e + 1] = k1 < len ? T[k1 * P + jj] : 0.0;
+  }
 }
 
 // ------------------------------------------------------------ large-system path (mhe_big.h)
@@ -309,8 +329,10 @@ unsigned long long const_tag(const mhe_dims* dm, int NT) {
     h *= 1099511628211ull;
   };
   // the path bit: 0 register-resident, 1 large-system, 2 fused-general (k_gn_general's layout)
+  // CONST_LAYOUT_REV and NW: a buffer laid out by a library with other tables, or with streams
+  // for another wave count, is refused like one of other dims
   const long long v[] = {0x4D4845, is_big(dm) ? 1 : fg_eligible(dm) ? 2 : 0, dm->N, dm->n, dm->m, dm->p, dm->M, dm->q, dm->dyn_model,
-                         dm->meas_model, dm->has_prior, dm->dyn_cost, NT, dm->n_eq, dm->n_extra};
+                         dm->meas_model, dm->has_prior, dm->dyn_cost, NT, dm->n_eq, dm->n_extra, CONST_LAYOUT_REV, NW};
   for (long long x : v) mix(x);
   if (dm->n_eq > 0 && dm->eq_idx)  // check_dims has validated n_eq <= MHE_MAX_EQ and eq_idx
     for (int i = 0; i < 2 * dm->n_eq; ++i) mix(dm->eq_idx[i]);
